@@ -6,7 +6,13 @@ HBM").  A "step" = one full q6 pass over the SF100-shaped lineitem columns
 (600,037,902 rows pinned by tpch_plan_stability/fixtures.rs:50; synthetic —
 no network for real dbgen data).
 
-Contract: python bench.py --gpus N --steps K --warmup W
+Contract: python bench.py --gpus N --steps K --warmup W [--full]
+                          [--dump-outputs DIR]
+  - a plain run does only what the headline figure needs: set up, warm up,
+    time the K steps, print the result line.  --full adds every other
+    measurement (today: the cpu_baseline leg).  --dump-outputs DIR writes
+    what the last timed step returned to its caller as DIR/<name>.npy
+    (float64); inputs are seeded, so two builds compare output for output.
   - W untimed warmup steps, then exactly K timed steps bracketed by a
     barrier + torch.cuda.synchronize() on both sides; MAX over ranks;
     rank 0 prints ONE JSON line.
@@ -21,7 +27,7 @@ Contract: python bench.py --gpus N --steps K --warmup W
     traffic from profiles/pmc_q6.json when a PMC calibration exists.
   - cpu_baseline: the oracle's q6 C path (kind "port", test infrastructure
     used here only as the reported baseline) timed on this box's host cores
-    over a bounded sample.
+    over a bounded sample.  Only with --full.
 """
 
 import argparse
@@ -50,8 +56,16 @@ def parse_args():
                         "contract); q5: q5-class hash-repartition resident "
                         "shuffle (hash->split->all-to-all->final agg, "
                         "SURVEY.md §8e)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements the headline figure does "
+                        "not need (the all-core cpu_baseline leg); off by "
+                        "default so a plain run stays lean")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step returned as DIR/<name>.npy (float64)")
     p.add_argument("--cpu-sample-rows", type=int, default=100_000_000)
-    p.add_argument("--skip-cpu-baseline", action="store_true")
+    p.add_argument("--skip-cpu-baseline", action="store_true",
+                   help="with --full: leave the cpu_baseline leg out")
     return p.parse_args()
 
 
@@ -84,6 +98,17 @@ def limbs_to_i128(limbs):
     if u >= 1 << 127:
         u -= 1 << 128
     return u
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one float64 .npy per named output of the last timed
+    step.  Exact integers wider than 2^53 go out as 32-bit limbs (little
+    endian), each exact in float64, next to their rounded float64 value."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, vals in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"),
+                np.asarray(vals, dtype=np.float64))
 
 
 def cpu_baseline_leg(sample_rows: int):
@@ -190,6 +215,7 @@ def q5_mode(args, dist, rank, world, local_rank):
     ev1 = torch.cuda.Event(enable_timing=True)
     repart_ms = []
     checked = {"ownership": False}
+    last = {}
 
     def step():
         kc = col_of(keys, gpu.BG_DT_INT64)
@@ -265,6 +291,8 @@ def q5_mode(args, dist, rank, world, local_rank):
             owners = pids // k_local
             assert (owners == rank).all(), "foreign rows received"
             checked["ownership"] = True
+        last.update(rows_received=m, groups=int(ng.value),
+                    price_sum=part_sum)
         return m
 
     def barrier_sync():
@@ -326,6 +354,15 @@ def q5_mode(args, dist, rank, world, local_rank):
             },
             "cpu_baseline": None,
         }
+    if args.dump_outputs:
+        # this rank's final-aggregate inputs and group count, last step
+        dump_outputs(args.dump_outputs, {
+            f"rows_received_rank{rank}": [last["rows_received"]],
+            f"groups_rank{rank}": [last["groups"]],
+            f"price_sum_rank{rank}": [float(last["price_sum"])],
+            f"price_sum_limbs_rank{rank}": i128_to_limbs(last["price_sum"]),
+        })
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
@@ -396,6 +433,15 @@ def main():
         dist.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if rank == 0 and args.dump_outputs:
+        # what the caller of the timed path received in the last step: the
+        # selected-row count and the exact Decimal128 revenue sum
+        dump_outputs(args.dump_outputs, {
+            "q6_count": [cnt],
+            "q6_sum": [float(total)],
+            "q6_sum_limbs": i128_to_limbs(total),
+        })
+
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1000.0
         total_rows = n * world * args.steps
@@ -456,7 +502,7 @@ def main():
             },
             "cpu_baseline": None,
         }
-        if not args.skip_cpu_baseline and world == 1:
+        if args.full and not args.skip_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline_leg(args.cpu_sample_rows)
         print(json.dumps(out), flush=True)
 
