@@ -1118,49 +1118,133 @@ extern "C" int bg_hash_repartition(const bg_column* key_cols, int32_t nkeys,
 
 // ---------------------------------------------------------------------------
 // q6: fused scan + filter + SUM(l_extendedprice * l_discount)
-// 52 B/row algorithmic (Date32 4 + 3 x Decimal128 16) — HBM-bound.
+//
+// Staged short-circuit scan.  The predicate is a conjunction of pure
+// comparisons, so a row that fails the date window can never need its
+// discount, and one that fails date or discount can never need its
+// quantity.  Columns are loaded in the order shipdate -> discount ->
+// quantity -> extendedprice, each only by lanes whose row passed every
+// earlier test; the memory pipeline fetches a 128-B line only if a live
+// lane addresses it, so HBM traffic is 4 B/row of dates plus the lines of
+// each later column that hold a survivor (TPC-H q6: 14.4 % / 3.9 % / 1.8 %
+// of rows survive the three tests) instead of 36 B/row + price lines.
+//
+// Done row-at-a-time that is four dependent HBM round trips, so each thread
+// owns BG_Q6_U rows of a BG_BLOCK*BG_Q6_U-row tile (row = tile_base +
+// u*BG_BLOCK + threadIdx.x: every wave instruction stays contiguous, 256 B
+// of dates / 1 KB of decimals) and a stage issues all of its loads before
+// any of them is consumed.  Comparisons stay on the full 128-bit value.
+// Column bases are only assumed element-aligned (4 B / 16 B).
 // ---------------------------------------------------------------------------
+#ifndef BG_Q6_U
+#define BG_Q6_U 8
+#endif
+
+// One Decimal128 as a clang vector: stays one 4-VGPR tuple from the load to
+// its use (HIP_vector_type isn't a clang vector and would be split).
+typedef unsigned long long q6_dec __attribute__((ext_vector_type(2)));
+
 template <bool NT>
-__global__ void k_q6_agg(const int32_t* shipdate, const ulong2* discount,
-                         const ulong2* quantity, const ulong2* extendedprice,
-                         int64_t n, int32_t date_lo, int32_t date_hi,
-                         i64 disc_lo, i64 disc_hi, i64 qty_lt, u64* out_lo,
-                         u64* out_hi, u64* out_count) {
+__device__ __forceinline__ q6_dec q6_load_dec(const ulong2* p) {
+  // NT: every byte is read at most once per pass — non-temporal loads skip
+  // L2 retention.
+  const q6_dec* q = reinterpret_cast<const q6_dec*>(p);
+  return NT ? __builtin_nontemporal_load(q) : *q;
+}
+
+// Stage boundary: every value of the finished stage is pinned in its
+// register here, so the compiler waits for the whole stage once and cannot
+// sink one row's test between the next stage's loads — where, loads
+// returning in order, the wait would also cover the loads just issued.
+__device__ __forceinline__ void q6_stage_end(int32_t (&d)[BG_Q6_U]) {
+#pragma unroll
+  for (int u = 0; u < BG_Q6_U; ++u) asm volatile("" : "+v"(d[u]) : : "memory");
+}
+__device__ __forceinline__ void q6_stage_end(q6_dec (&v)[BG_Q6_U]) {
+#pragma unroll
+  for (int u = 0; u < BG_Q6_U; ++u) asm volatile("" : "+v"(v[u]) : : "memory");
+}
+
+// Stage 1 of one tile: U date loads per thread, nothing consumed.  The loads
+// are unconditional — a row past the end reads row n-1 instead and is
+// discarded by the caller's `i < n` test — so their number is the same on
+// every path and the compiler's wait counts stay exact.  Needs n >= 1.
+template <bool NT>
+__device__ __forceinline__ void q6_load_dates(const int32_t* shipdate,
+                                              int64_t row0, int64_t n,
+                                              int32_t (&d)[BG_Q6_U]) {
+#pragma unroll
+  for (int u = 0; u < BG_Q6_U; ++u) {
+    int64_t i = row0 + (int64_t)u * BG_BLOCK;
+    if (i >= n) i = n - 1;
+    d[u] = NT ? __builtin_nontemporal_load(&shipdate[i]) : shipdate[i];
+  }
+}
+
+template <bool NT>
+__global__ __launch_bounds__(BG_BLOCK) void k_q6_agg(
+    const int32_t* shipdate, const ulong2* discount, const ulong2* quantity,
+    const ulong2* extendedprice, int64_t n, int32_t date_lo, int32_t date_hi,
+    i64 disc_lo, i64 disc_hi, i64 qty_lt, u64* out_lo, u64* out_hi,
+    u64* out_count) {
+  constexpr int U = BG_Q6_U;
+  constexpr int64_t T = (int64_t)BG_BLOCK * U;
+  const int64_t ntiles = (n + T - 1) / T;
   i128 acc = 0;
   u64 cnt = 0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    // NT: every byte is read exactly once per pass — non-temporal loads
-    // skip L2 retention (guide §nt-weights: streams one CU reads once).
-    // HIP_vector_type isn't a clang vector: load via ext_vector alias.
-    typedef unsigned long long ull2_ev __attribute__((ext_vector_type(2)));
-    int32_t d;
-    ulong2 dv, qv, pv;
-    if (NT) {
-      d = __builtin_nontemporal_load(&shipdate[i]);
-      const ull2_ev dve = __builtin_nontemporal_load(
-          reinterpret_cast<const ull2_ev*>(discount) + i);
-      const ull2_ev qve = __builtin_nontemporal_load(
-          reinterpret_cast<const ull2_ev*>(quantity) + i);
-      const ull2_ev pve = __builtin_nontemporal_load(
-          reinterpret_cast<const ull2_ev*>(extendedprice) + i);
-      dv.x = dve[0]; dv.y = dve[1];
-      qv.x = qve[0]; qv.y = qve[1];
-      pv.x = pve[0]; pv.y = pve[1];
-    } else {
-      d = shipdate[i];
-      dv = discount[i];
-      qv = quantity[i];
-      pv = extendedprice[i];
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t row0 = tile * T + threadIdx.x;
+    // stage 1: dates
+    int32_t d[U];
+    q6_load_dates<NT>(shipdate, row0, n, d);
+    q6_stage_end(d);
+    bool live[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      live[u] = (row0 + (int64_t)u * BG_BLOCK < n) & (d[u] >= date_lo) &
+                (d[u] < date_hi);
+    // stage 2: discount, only where the date passed
+    q6_dec v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      v[u] = q6_dec{0, 0};
+      if (live[u])
+        v[u] = q6_load_dec<NT>(discount + row0 + (int64_t)u * BG_BLOCK);
     }
-    const i128 disc = make_i128(dv.x, (i64)dv.y);
-    const i128 qty = make_i128(qv.x, (i64)qv.y);
-    const bool keep = (d >= date_lo) & (d < date_hi) & (disc >= disc_lo) &
-                      (disc <= disc_hi) & (qty < qty_lt);
-    if (keep) {
-      const i128 price = make_i128(pv.x, (i64)pv.y);
-      acc += price * disc;
-      cnt++;
+    q6_stage_end(v);
+    // a discount inside [disc_lo, disc_hi] fits i64: keep the low limb only
+    i64 disc[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const i128 x = make_i128(v[u][0], (i64)v[u][1]);
+      live[u] = live[u] & (x >= disc_lo) & (x <= disc_hi);
+      disc[u] = (i64)v[u][0];
+    }
+    // stage 3: quantity, only where date and discount passed
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      v[u] = q6_dec{0, 0};
+      if (live[u])
+        v[u] = q6_load_dec<NT>(quantity + row0 + (int64_t)u * BG_BLOCK);
+    }
+    q6_stage_end(v);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      live[u] = live[u] & (make_i128(v[u][0], (i64)v[u][1]) < qty_lt);
+    // stage 4: price, only for selected rows
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      v[u] = q6_dec{0, 0};
+      if (live[u])
+        v[u] = q6_load_dec<NT>(extendedprice + row0 + (int64_t)u * BG_BLOCK);
+    }
+    q6_stage_end(v);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (live[u]) {
+        acc += make_i128(v[u][0], (i64)v[u][1]) * (i128)disc[u];
+        cnt++;
+      }
     }
   }
   // wave -> block -> global
@@ -1188,6 +1272,38 @@ __global__ void k_q6_agg(const int32_t* shipdate, const ulong2* discount,
   }
 }
 
+// Per-thread fixed state of bg_q6_agg: at ~2 ms per call, creating and
+// destroying two events, a blocking memset and a pageable copy per call are
+// no longer noise.  Events and the pinned result words are made once per
+// (thread, device) and reused.
+struct Q6HostState {
+  int device = -1;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  u64* h_res = nullptr;  // pinned [lo, hi, count]
+};
+static thread_local Q6HostState g_q6;
+
+static int q6_host_state(Q6HostState** out) {
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (g_q6.device != dev) {
+    if (g_q6.device >= 0) {  // the thread moved to another device
+      (void)hipEventDestroy(g_q6.ev0);
+      (void)hipEventDestroy(g_q6.ev1);
+      (void)hipHostFree(g_q6.h_res);
+      g_q6 = Q6HostState();
+    }
+    Q6HostState st;
+    HIP_TRY(hipEventCreate(&st.ev0));
+    HIP_TRY(hipEventCreate(&st.ev1));
+    HIP_TRY(hipHostMalloc((void**)&st.h_res, 3 * sizeof(u64)));
+    st.device = dev;
+    g_q6 = st;
+  }
+  *out = &g_q6;
+  return BG_OK;
+}
+
 extern "C" int bg_q6_agg(const bg_column* shipdate, const bg_column* discount,
                          const bg_column* quantity,
                          const bg_column* extendedprice, int32_t date_lo,
@@ -1198,16 +1314,17 @@ extern "C" int bg_q6_agg(const bg_column* shipdate, const bg_column* discount,
   if (shipdate->dtype != BG_DT_DATE32 && shipdate->dtype != BG_DT_INT32)
     return set_err(BG_ERR_INVALID, "shipdate must be DATE32");
   const int64_t n = shipdate->len;
+  Q6HostState* st;
+  if (int rc = q6_host_state(&st)) return rc;
   u64* d_acc;  // [lo, hi, count]
   HIP_TRY(pool_malloc((void**)&d_acc, 3 * sizeof(u64)));
-  HIP_TRY(hipMemset(d_acc, 0, 3 * sizeof(u64)));
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
+  HIP_TRY(hipMemsetAsync(d_acc, 0, 3 * sizeof(u64), 0));
+  // one block per tile, grid-stride beyond the cap
+  const int64_t tile = (int64_t)BG_BLOCK * BG_Q6_U;
+  int blocks = (int)bg_imin64((n + tile - 1) / tile, BG_MAX_BLOCKS);
   if (blocks == 0) blocks = 1;
-  hipEvent_t ev0, ev1;
-  HIP_TRY(hipEventCreate(&ev0));
-  HIP_TRY(hipEventCreate(&ev1));
-  HIP_TRY(hipEventRecord(ev0, 0));
-  // non-temporal loads by default: the fused scan reads every byte exactly
+  HIP_TRY(hipEventRecord(st->ev0, 0));
+  // non-temporal loads by default: the fused scan reads every byte at most
   // once, and NT streams measured +11% over cached loads (6.7 vs 6.05 TB/s)
   static const bool use_nt = [] {
     const char* e = getenv("BG_Q6_NT");
@@ -1230,19 +1347,18 @@ extern "C" int bg_q6_agg(const bg_column* shipdate, const bg_column* discount,
                        date_hi, disc_lo, disc_hi, qty_lt, d_acc, d_acc + 1,
                        d_acc + 2);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ev1, 0));
-  HIP_TRY(hipEventSynchronize(ev1));
+  // ev0/ev1 bracket the kernel alone; the readback rides behind ev1
+  HIP_TRY(hipEventRecord(st->ev1, 0));
+  HIP_TRY(hipMemcpyAsync(st->h_res, d_acc, 3 * sizeof(u64),
+                         hipMemcpyDeviceToHost, 0));
+  HIP_TRY(hipStreamSynchronize(0));
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+  HIP_TRY(hipEventElapsedTime(&ms, st->ev0, st->ev1));
   g_last_kernel_ms = (double)ms;
-  HIP_TRY(hipEventDestroy(ev0));
-  HIP_TRY(hipEventDestroy(ev1));
-  u64 h[3];
-  HIP_TRY(hipMemcpy(h, d_acc, 3 * sizeof(u64), hipMemcpyDeviceToHost));
   HIP_TRY(pool_release(d_acc));
-  *out_sum_lo = h[0];
-  *out_sum_hi = (int64_t)h[1];
-  *out_count = (int64_t)h[2];
+  *out_sum_lo = st->h_res[0];
+  *out_sum_hi = (int64_t)st->h_res[1];
+  *out_count = (int64_t)st->h_res[2];
   return BG_OK;
 }
 
