@@ -28,6 +28,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <mutex>
+#include <set>
+#include <unordered_map>
+#include <utility>
+#include <vector>
 
 #include "../../include/ballista_gpu.h"
 #include "bg_ahash.h"
@@ -50,10 +56,12 @@ static thread_local bool g_inited = false;
 static thread_local double g_last_kernel_ms = 0.0;
 
 extern "C" const char* bg_last_error(void) { return g_err; }
-extern "C" int bg_version(void) { return 10; }
+extern "C" int bg_version(void) { return 11; }
 
-// Build provenance: the sha256 over (kernels.hip, bg_ahash.h,
-// ballista_gpu.h) injected by __graft_entry__.build(); a CPU test
+// Build provenance: the sha256 over the library's seven sources
+// (kernels.hip, bg_ahash.h, stage.cpp, stage_ipc.h, stage_json.h,
+// stage_parquet.h, ballista_gpu.h) injected by __graft_entry__.build(); a
+// CPU test
 // recomputes the hash over the committed sources and fails when the
 // committed .so was not built from them.
 #ifndef BG_SOURCE_HASH
@@ -89,16 +97,15 @@ static int set_hip_err(hipError_t e, const char* what) {
 // free list (power-of-two rounding, per-process, mutex-guarded).  Sized for
 // 288 GB HBM: memory stays pooled until bg_pool_trim().
 // ---------------------------------------------------------------------------
-#include <map>
-#include <mutex>
-#include <set>
-#include <unordered_map>
-#include <vector>
-
 static std::mutex g_pool_mu;
 static std::unordered_map<uint64_t, std::vector<void*>> g_pool_free;
 static std::unordered_map<void*, uint64_t> g_pool_sizes;
 static std::set<void*> g_pool_freeset;
+// accounting for bg_pool_stats(), kept under g_pool_mu: buffers handed out
+// and not yet released ("live"), and bytes parked in the free lists
+static int64_t g_pool_live_bytes = 0;
+static int64_t g_pool_live_buffers = 0;
+static int64_t g_pool_cached_bytes = 0;
 
 static uint64_t pool_round(uint64_t bytes) {
   uint64_t p = 256;
@@ -115,6 +122,9 @@ static hipError_t pool_malloc(void** out, uint64_t bytes) {
       *out = it->second.back();
       it->second.pop_back();
       g_pool_freeset.erase(*out);
+      g_pool_cached_bytes -= (int64_t)sz;
+      g_pool_live_bytes += (int64_t)sz;
+      ++g_pool_live_buffers;
       return hipSuccess;
     }
   }
@@ -127,11 +137,15 @@ static hipError_t pool_malloc(void** out, uint64_t bytes) {
         (void)hipFree(p);
       }
     g_pool_free.clear();
+    g_pool_freeset.clear();
+    g_pool_cached_bytes = 0;
     e = hipMalloc(out, sz);
   }
   if (e == hipSuccess) {
     std::lock_guard<std::mutex> g(g_pool_mu);
     g_pool_sizes[*out] = sz;
+    g_pool_live_bytes += (int64_t)sz;
+    ++g_pool_live_buffers;
   }
   return e;
 }
@@ -149,6 +163,9 @@ static hipError_t pool_release(void* p) {
     abort();
   }
   g_pool_free[it->second].push_back(p);
+  g_pool_live_bytes -= (int64_t)it->second;
+  --g_pool_live_buffers;
+  g_pool_cached_bytes += (int64_t)it->second;
   return hipSuccess;
 }
 
@@ -160,6 +177,110 @@ extern "C" int bg_pool_trim(void) {
       (void)hipFree(p);
     }
   g_pool_free.clear();
+  g_pool_freeset.clear();
+  g_pool_cached_bytes = 0;
+  return BG_OK;
+}
+
+extern "C" int bg_pool_stats(int64_t* live_bytes, int64_t* live_buffers,
+                             int64_t* cached_bytes) {
+  std::lock_guard<std::mutex> g(g_pool_mu);
+  if (live_bytes) *live_bytes = g_pool_live_bytes;
+  if (live_buffers) *live_buffers = g_pool_live_buffers;
+  if (cached_bytes) *cached_bytes = g_pool_cached_bytes;
+  return BG_OK;
+}
+
+// Scoped owner of one pooled device buffer: released when it goes out of
+// scope, so every return path of a host wrapper (HIP_TRY included) gives
+// its temporaries back.  Releasing at scope exit, with kernels that read
+// the buffer possibly still in flight, is safe because ALL library work is
+// issued on the one legacy null stream (every launch and every async
+// memset/copy in this file passes stream 0, bg_q6_agg included, the
+// blocking hipMemcpy/hipMemset calls use it implicitly, and no other
+// stream is ever created): whoever takes the buffer from the pool next can
+// only touch it with work that the stream orders after its previous user.
+template <typename T>
+struct DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      reset();
+      p = o.p;
+      o.p = nullptr;
+    }
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  // count == 0 still allocates one element: callers pass the pointer on
+  hipError_t alloc(int64_t count) {
+    reset();
+    void* q = nullptr;
+    hipError_t e = pool_malloc(&q, sizeof(T) * (uint64_t)(count ? count : 1));
+    if (e == hipSuccess) p = (T*)q;
+    return e;
+  }
+  void reset() {
+    if (p) (void)pool_release(p);
+    p = nullptr;
+  }
+  // hand the pointer to a longer-lived owner (join handles)
+  T* detach() {
+    T* q = p;
+    p = nullptr;
+    return q;
+  }
+  void swap(DevBuf& o) { std::swap(p, o.p); }
+  T* get() const { return p; }
+  operator T*() const { return p; }
+};
+
+// Scoped pair of timing events (create-per-call, destroyed on every path).
+struct EventPair {
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  EventPair() = default;
+  EventPair(const EventPair&) = delete;
+  EventPair& operator=(const EventPair&) = delete;
+  ~EventPair() {
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+  }
+  hipError_t create() {
+    hipError_t e = hipEventCreate(&ev0);
+    return e != hipSuccess ? e : hipEventCreate(&ev1);
+  }
+};
+
+// grid size for `items` work items at `per_block` items per block:
+// ceil(items / per_block), capped at BG_MAX_BLOCKS, never 0
+static inline int grid_for(int64_t items, int64_t per_block = BG_BLOCK) {
+  const int64_t b = bg_imin64((items + per_block - 1) / per_block,
+                              BG_MAX_BLOCKS);
+  return b < 1 ? 1 : (int)b;
+}
+
+// The shared body of the bg_*_batch wrappers: upload `njobs` host job
+// records, zero an int error flag, launch kernel(jobs, njobs, extra...,
+// flag) on `blocks` blocks and read the flag back into *err_out.  The
+// caller keeps its own grid rule and its own flag -> error mapping.
+template <typename Job, typename Kernel, typename... Extra>
+static int run_job_batch(Kernel kernel, const void* h_jobs, int64_t njobs,
+                         int blocks, int* err_out, Extra... extra) {
+  DevBuf<Job> d_jobs;
+  DevBuf<int> d_err;
+  HIP_TRY(d_jobs.alloc(njobs));
+  HIP_TRY(d_err.alloc(1));
+  HIP_TRY(hipMemset(d_err, 0, sizeof(int)));
+  HIP_TRY(hipMemcpy(d_jobs, h_jobs, sizeof(Job) * njobs,
+                    hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(BG_BLOCK), 0, 0, d_jobs.get(),
+                     njobs, extra..., d_err.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(err_out, d_err, sizeof(int), hipMemcpyDeviceToHost));
   return BG_OK;
 }
 
@@ -400,9 +521,7 @@ extern "C" int bg_eval_predicates(const bg_column* cols, int32_t ncols,
     a.p[i].hi_hi = preds[i].hi_hi;
   }
   int64_t nwords = (n + 63) / 64;
-  int blocks = (int)bg_imin64((nwords * BG_WAVE + BG_BLOCK - 1) / BG_BLOCK,
-                                 BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(nwords * BG_WAVE);
   hipLaunchKernelGGL(k_eval_predicates, dim3(blocks), dim3(BG_BLOCK), 0, 0, a,
                      n, reinterpret_cast<u64*>(d_mask), nwords);
   HIP_TRY(hipGetLastError());
@@ -589,12 +708,12 @@ static int scan_exclusive_t(const IN* d_in, int64_t m, i64* d_out,
   const char* envs = getenv("BG_SCAN_LOOKBACK");
   if (sizeof(IN) == 8 && envs && envs[0] == '1') {
     const int64_t ntiles = (m + SCAN_TILE - 1) / SCAN_TILE;
-    u64* d_state;
-    int* d_ticket;
+    DevBuf<u64> d_state;
+    DevBuf<int> d_ticket;
     hipError_t e;
-    e = pool_malloc((void**)&d_state, sizeof(u64) * ntiles);
+    e = d_state.alloc(ntiles);
     if (e != hipSuccess) return set_hip_err(e, "scan malloc");
-    e = pool_malloc((void**)&d_ticket, sizeof(int));
+    e = d_ticket.alloc(1);
     if (e != hipSuccess) return set_hip_err(e, "scan malloc");
     e = hipMemsetAsync(d_state, 0, sizeof(u64) * ntiles, 0);
     if (e != hipSuccess) return set_hip_err(e, "scan memset");
@@ -605,31 +724,28 @@ static int scan_exclusive_t(const IN* d_in, int64_t m, i64* d_out,
                        (const u64*)(const void*)d_in, m, d_out, d_total,
                        d_state, d_ticket, ntiles);
     e = hipGetLastError();
-    (void)pool_release(d_state);
-    (void)pool_release(d_ticket);
     if (e != hipSuccess) return set_hip_err(e, "scan lookback");
     return BG_OK;
   }
   const int64_t seg = 1 << 16;  // 65536 elems per block segment
   const int64_t nseg = (m + seg - 1) / seg;
-  u64* d_segsums;
-  i64* d_segbases;
+  DevBuf<u64> d_segsums;
+  DevBuf<i64> d_segbases;
   hipError_t e;
-  e = pool_malloc((void**)&d_segsums, sizeof(u64) * nseg);
+  e = d_segsums.alloc(nseg);
   if (e != hipSuccess) return set_hip_err(e, "scan malloc");
-  e = pool_malloc((void**)&d_segbases, sizeof(i64) * nseg);
+  e = d_segbases.alloc(nseg);
   if (e != hipSuccess) return set_hip_err(e, "scan malloc");
   int blocks = (int)bg_imin64(nseg, BG_MAX_BLOCKS);
   hipLaunchKernelGGL(k_segment_sums_i64, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      d_in, m, seg, d_segsums, nseg);
   hipLaunchKernelGGL(k_exclusive_scan_i64, dim3(1), dim3(BG_BLOCK), 0, 0,
-                     d_segsums, nseg, d_segbases, d_total, nseg, nullptr);
+                     d_segsums.get(), nseg, d_segbases.get(), d_total, nseg,
+                     nullptr);
   hipLaunchKernelGGL(k_exclusive_scan_i64, dim3((uint32_t)nseg),
                      dim3(BG_BLOCK), 0, 0, d_in, m, d_out, nullptr, seg,
                      d_segbases);
   e = hipGetLastError();
-  (void)pool_release(d_segsums);
-  (void)pool_release(d_segbases);
   if (e != hipSuccess) return set_hip_err(e, "scan large");
   return BG_OK;
 }
@@ -700,14 +816,13 @@ extern "C" int bg_mask_to_indices(const uint8_t* d_mask, int64_t n,
   REQUIRE_INIT();
   const int64_t nwords = (n + 63) / 64;
   const int64_t nchunks = (nwords + MC_WORDS_PER_WAVE - 1) / MC_WORDS_PER_WAVE;
-  u64* d_counts;
-  i64* d_offs;
-  i64* d_total;
-  HIP_TRY(pool_malloc((void**)&d_counts, sizeof(u64) * (nchunks ? nchunks : 1)));
-  HIP_TRY(pool_malloc((void**)&d_offs, sizeof(i64) * (nchunks ? nchunks : 1)));
-  HIP_TRY(pool_malloc((void**)&d_total, sizeof(i64)));
-  int blocks = (int)bg_imin64(nchunks, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  DevBuf<u64> d_counts;
+  DevBuf<i64> d_offs;
+  DevBuf<i64> d_total;
+  HIP_TRY(d_counts.alloc(nchunks));
+  HIP_TRY(d_offs.alloc(nchunks));
+  HIP_TRY(d_total.alloc(1));
+  int blocks = grid_for(nchunks, 1);
   hipLaunchKernelGGL(k_mask_count, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      reinterpret_cast<const u64*>(d_mask), nwords, n, d_counts,
                      nchunks);
@@ -720,9 +835,6 @@ extern "C" int bg_mask_to_indices(const uint8_t* d_mask, int64_t n,
                      nchunks, d_indices);
   i64 total = 0;
   HIP_TRY(hipMemcpy(&total, d_total, sizeof(i64), hipMemcpyDeviceToHost));
-  HIP_TRY(pool_release(d_counts));
-  HIP_TRY(pool_release(d_offs));
-  HIP_TRY(pool_release(d_total));
   *out_count = total;
   return BG_OK;
 }
@@ -740,8 +852,7 @@ __global__ void k_gather(const T* src, const uint32_t* idx, int64_t m, T* dst) {
 extern "C" int bg_gather(const void* d_src, int64_t elem_size,
                          const uint32_t* d_idx, int64_t m, void* d_dst) {
   REQUIRE_INIT();
-  int blocks = (int)bg_imin64((m + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(m);
   switch (elem_size) {
     case 1:
       hipLaunchKernelGGL(k_gather<uint8_t>, dim3(blocks), dim3(BG_BLOCK), 0, 0,
@@ -844,8 +955,7 @@ extern "C" int bg_hash_columns(const bg_column* key_cols, int32_t nkeys,
     a.k[i].offsets = key_cols[i].d_offsets;
     a.k[i].dtype = key_cols[i].dtype;
   }
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(n);
   hipLaunchKernelGGL(k_hash_columns, dim3(blocks), dim3(BG_BLOCK), 0, 0, a, n,
                      reinterpret_cast<u64*>(d_hashes));
   HIP_TRY(hipGetLastError());
@@ -863,8 +973,7 @@ extern "C" int bg_partition_ids(const uint64_t* d_hashes, int64_t n, uint32_t k,
                                 uint32_t* d_pids) {
   REQUIRE_INIT();
   if (k == 0) return set_err(BG_ERR_INVALID, "k == 0");
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(n);
   hipLaunchKernelGGL(k_partition_ids, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      reinterpret_cast<const u64*>(d_hashes), n, k, d_pids);
   HIP_TRY(hipGetLastError());
@@ -996,13 +1105,12 @@ extern "C" int bg_partition_indices_ex(const uint32_t* d_pids, int64_t n,
   const int waves_per_block = BG_BLOCK / BG_WAVE;
   const size_t lds_hist = (size_t)waves_per_block * k * sizeof(uint32_t);
   const size_t lds_scat = (size_t)waves_per_block * k * sizeof(i64);
-  u64* d_hist;
-  i64* d_start;
+  DevBuf<u64> d_hist;
+  DevBuf<i64> d_start;
   const int64_t hist_len = (int64_t)k * (nchunks ? nchunks : 1);
-  HIP_TRY(pool_malloc((void**)&d_hist, sizeof(u64) * hist_len));
-  HIP_TRY(pool_malloc((void**)&d_start, sizeof(i64) * hist_len));
-  int blocks = (int)bg_imin64(nchunks, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  HIP_TRY(d_hist.alloc(hist_len));
+  HIP_TRY(d_start.alloc(hist_len));
+  int blocks = grid_for(nchunks, 1);
   hipLaunchKernelGGL(k_part_hist, dim3(blocks), dim3(BG_BLOCK), lds_hist, 0,
                      d_pids, n, k, d_hist, nchunks);
   {
@@ -1015,8 +1123,6 @@ extern "C" int bg_partition_indices_ex(const uint32_t* d_pids, int64_t n,
                      d_pids, n, k, d_start, nchunks, d_indices, d_rank);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(pool_release(d_hist));
-  HIP_TRY(pool_release(d_start));
   return BG_OK;
 }
 
@@ -1045,8 +1151,7 @@ extern "C" int bg_scatter_rows(const void* d_src, int64_t elem_size,
                                const uint32_t* d_rank, int64_t n,
                                void* d_dst) {
   REQUIRE_INIT();
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(n);
   switch (elem_size) {
     case 1:
       hipLaunchKernelGGL(k_scatter_rows<uint8_t>, dim3(blocks), dim3(BG_BLOCK),
@@ -1088,32 +1193,23 @@ extern "C" int bg_hash_repartition(const bg_column* key_cols, int32_t nkeys,
                                    int64_t* d_offsets, void** d_out) {
   REQUIRE_INIT();
   if (ncols > BG_MAX_PAYLOAD) return set_err(BG_ERR_INVALID, "too many payload cols");
-  uint64_t* d_hashes;
-  uint32_t* d_pids;
-  uint32_t* d_rank;
-  HIP_TRY(pool_malloc((void**)&d_hashes, sizeof(u64) * (n ? n : 1)));
-  HIP_TRY(pool_malloc((void**)&d_pids, sizeof(uint32_t) * (n ? n : 1)));
-  HIP_TRY(pool_malloc((void**)&d_rank, sizeof(uint32_t) * (n ? n : 1)));
+  DevBuf<uint64_t> d_hashes;
+  DevBuf<uint32_t> d_pids;
+  DevBuf<uint32_t> d_rank;
+  HIP_TRY(d_hashes.alloc(n));
+  HIP_TRY(d_pids.alloc(n));
+  HIP_TRY(d_rank.alloc(n));
   int rc = bg_hash_columns(key_cols, nkeys, n, d_hashes);
   if (rc == BG_OK) rc = bg_partition_ids(d_hashes, n, k, d_pids);
   if (rc == BG_OK)
     rc = bg_partition_indices_ex(d_pids, n, k, d_indices, d_offsets, d_rank);
-  if (rc == BG_OK) {
-    for (int c = 0; c < ncols && rc == BG_OK; ++c) {
-      int64_t esz = dtype_size(payload_cols[c].dtype);
-      if (esz == 0) { rc = set_err(BG_ERR_UNSUPPORTED, "payload dtype"); break; }
-      // sequential-read scatter through the inverse permutation
-      rc = bg_scatter_rows(payload_cols[c].d_data, esz, d_rank, n, d_out[c]);
-    }
+  for (int c = 0; c < ncols && rc == BG_OK; ++c) {
+    int64_t esz = dtype_size(payload_cols[c].dtype);
+    if (esz == 0) return set_err(BG_ERR_UNSUPPORTED, "payload dtype");
+    // sequential-read scatter through the inverse permutation
+    rc = bg_scatter_rows(payload_cols[c].d_data, esz, d_rank, n, d_out[c]);
   }
-  hipError_t e1 = pool_release(d_hashes);
-  hipError_t e2 = pool_release(d_pids);
-  hipError_t e3 = pool_release(d_rank);
-  if (rc != BG_OK) return rc;
-  if (e1 != hipSuccess) return set_hip_err(e1, "hipFree");
-  if (e2 != hipSuccess) return set_hip_err(e2, "hipFree");
-  if (e3 != hipSuccess) return set_hip_err(e3, "hipFree");
-  return BG_OK;
+  return rc;
 }
 
 // ---------------------------------------------------------------------------
@@ -1321,8 +1417,7 @@ extern "C" int bg_q6_agg(const bg_column* shipdate, const bg_column* discount,
   HIP_TRY(hipMemsetAsync(d_acc, 0, 3 * sizeof(u64), 0));
   // one block per tile, grid-stride beyond the cap
   const int64_t tile = (int64_t)BG_BLOCK * BG_Q6_U;
-  int blocks = (int)bg_imin64((n + tile - 1) / tile, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(n, tile);
   HIP_TRY(hipEventRecord(st->ev0, 0));
   // non-temporal loads by default: the fused scan reads every byte at most
   // once, and NT streams measured +11% over cached loads (6.7 vs 6.05 TB/s)
@@ -1436,18 +1531,15 @@ extern "C" int bg_q1_agg(const bg_column* rf, const bg_column* ls,
                          int64_t* h_counts, uint8_t* h_sums) {
   REQUIRE_INIT();
   const int64_t n = shipdate->len;
-  u64* d_sums;
-  u64* d_counts;
-  HIP_TRY(pool_malloc((void**)&d_sums, Q1_GROUPS * Q1_ACCS * 2 * sizeof(u64)));
-  HIP_TRY(pool_malloc((void**)&d_counts, Q1_GROUPS * sizeof(u64)));
+  DevBuf<u64> d_sums, d_counts;
+  HIP_TRY(d_sums.alloc(Q1_GROUPS * Q1_ACCS * 2));
+  HIP_TRY(d_counts.alloc(Q1_GROUPS));
   HIP_TRY(hipMemset(d_sums, 0, Q1_GROUPS * Q1_ACCS * 2 * sizeof(u64)));
   HIP_TRY(hipMemset(d_counts, 0, Q1_GROUPS * sizeof(u64)));
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
-  hipEvent_t ev0, ev1;
-  HIP_TRY(hipEventCreate(&ev0));
-  HIP_TRY(hipEventCreate(&ev1));
-  HIP_TRY(hipEventRecord(ev0, 0));
+  int blocks = grid_for(n);
+  EventPair ev;
+  HIP_TRY(ev.create());
+  HIP_TRY(hipEventRecord(ev.ev0, 0));
   hipLaunchKernelGGL(k_q1_agg, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      (const uint8_t*)rf->d_data, (const uint8_t*)ls->d_data,
                      (const ulong2*)quantity->d_data,
@@ -1457,19 +1549,15 @@ extern "C" int bg_q1_agg(const bg_column* rf, const bg_column* ls,
                      (const int32_t*)shipdate->d_data, n, date_le, d_sums,
                      d_counts);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ev1, 0));
-  HIP_TRY(hipEventSynchronize(ev1));
+  HIP_TRY(hipEventRecord(ev.ev1, 0));
+  HIP_TRY(hipEventSynchronize(ev.ev1));
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+  HIP_TRY(hipEventElapsedTime(&ms, ev.ev0, ev.ev1));
   g_last_kernel_ms = (double)ms;
-  HIP_TRY(hipEventDestroy(ev0));
-  HIP_TRY(hipEventDestroy(ev1));
   u64 sums[Q1_GROUPS * Q1_ACCS * 2];
   u64 counts[Q1_GROUPS];
   HIP_TRY(hipMemcpy(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost));
-  HIP_TRY(pool_release(d_sums));
-  HIP_TRY(pool_release(d_counts));
   for (int gidx = 0; gidx < Q1_GROUPS; ++gidx) {
     h_counts[gidx] = (int64_t)counts[gidx];
     for (int a = 0; a < Q1_ACCS; ++a) {
@@ -1614,17 +1702,21 @@ extern "C" int bg_hashjoin_build(const bg_column* build_keys, int64_t n,
   t.n_build = n;
   const u64 nb = next_pow2_u64((u64)(n > 4 ? n * 2 : 8));
   t.mask = nb - 1;
-  HIP_TRY(pool_malloc((void**)&t.nodes, sizeof(ulong2) * (n ? n : 1)));
-  HIP_TRY(pool_malloc((void**)&t.head, sizeof(int) * nb));
-  HIP_TRY(hipMemset(t.head, 0xff, sizeof(int) * nb));  // -1
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  DevBuf<ulong2> nodes;
+  DevBuf<int> head;
+  HIP_TRY(nodes.alloc(n));
+  HIP_TRY(head.alloc((int64_t)nb));
+  HIP_TRY(hipMemset(head, 0xff, sizeof(int) * nb));  // -1
+  int blocks = grid_for(n);
   hipLaunchKernelGGL(k_join_build, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      (const int64_t*)build_keys->d_data,
-                     build_keys->d_validity, n, t.head, t.nodes, t.mask);
+                     build_keys->d_validity, n, head.get(), nodes.get(),
+                     t.mask);
   HIP_TRY(hipGetLastError());
-  BgJoinTable* h = new BgJoinTable(t);
-  *out_handle = h;
+  // the handle owns the table from here; bg_hashjoin_free releases it
+  t.nodes = nodes.detach();
+  t.head = head.detach();
+  *out_handle = new BgJoinTable(t);
   return BG_OK;
 }
 
@@ -1642,14 +1734,13 @@ extern "C" int bg_hashjoin_probe_count(void* handle,
     (void)pool_release(t->probe_offsets);
     t->probe_offsets = nullptr;
   }
-  uint32_t* d_counts;
-  i64* d_offs;
-  i64* d_total;
-  HIP_TRY(pool_malloc((void**)&d_counts, sizeof(uint32_t) * (n ? n : 1)));
-  HIP_TRY(pool_malloc((void**)&d_offs, sizeof(i64) * (n ? n : 1)));
-  HIP_TRY(pool_malloc((void**)&d_total, sizeof(i64)));
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  DevBuf<uint32_t> d_counts;
+  DevBuf<i64> d_offs;
+  DevBuf<i64> d_total;
+  HIP_TRY(d_counts.alloc(n));
+  HIP_TRY(d_offs.alloc(n));
+  HIP_TRY(d_total.alloc(1));
+  int blocks = grid_for(n);
   hipLaunchKernelGGL(k_join_count, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      (const int64_t*)probe_keys->d_data,
                      probe_keys->d_validity, n, t->head, t->nodes,
@@ -1662,11 +1753,9 @@ extern "C" int bg_hashjoin_probe_count(void* handle,
   }
   i64 total = 0;
   HIP_TRY(hipMemcpy(&total, d_total, sizeof(i64), hipMemcpyDeviceToHost));
-  HIP_TRY(pool_release(d_counts));
   // stash offsets on the handle for the fill call
-  t->probe_offsets = d_offs;
+  t->probe_offsets = d_offs.detach();
   t->probe_n = n;
-  HIP_TRY(pool_release(d_total));
   *out_matches = total;
   return BG_OK;
 }
@@ -1679,8 +1768,7 @@ extern "C" int bg_hashjoin_probe_fill(void* handle,
   BgJoinTable* t = (BgJoinTable*)handle;
   if (!t->probe_offsets || t->probe_n != n)
     return set_err(BG_ERR_INVALID, "call bg_hashjoin_probe_count first");
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(n);
   hipLaunchKernelGGL(k_join_fill, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      (const int64_t*)probe_keys->d_data,
                      probe_keys->d_validity, n, t->head, t->nodes,
@@ -2173,15 +2261,14 @@ static int hashagg_impl(const bg_column* key_cols, int32_t nkeys,
   u64 cap = 8;
   while (cap < (u64)(max_groups * 2)) cap <<= 1;
   const int rec = 2 + (2 + vmode) * naggs;
-  u64* slot_data;
-  int* err_flag;
-  HIP_TRY(pool_malloc((void**)&slot_data, sizeof(u64) * cap * rec));
-  HIP_TRY(pool_malloc((void**)&err_flag, sizeof(int)));
+  DevBuf<u64> slot_data;
+  DevBuf<int> err_flag;
+  HIP_TRY(slot_data.alloc(cap * rec));
+  HIP_TRY(err_flag.alloc(1));
   HIP_TRY(hipMemset(slot_data, 0, sizeof(u64) * cap * rec));
   HIP_TRY(hipMemset(err_flag, 0, sizeof(int)));
 
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(n);
   // low-cardinality first attempt: per-block LDS tables (48 KB budget).
   // Overflow (more groups than the LDS capacity) aborts with err=2 and
   // we fall back to the global-table kernel on a zeroed table.
@@ -2189,10 +2276,9 @@ static int hashagg_impl(const bg_column* key_cols, int32_t nkeys,
   while (lds_cap * 2 * (u64)rec * 8 <= 48 * 1024 && lds_cap < 4096)
     lds_cap <<= 1;
   const bool try_lds = lds_cap >= 64 && n >= (1 << 16);
-  hipEvent_t ev0, ev1;
-  HIP_TRY(hipEventCreate(&ev0));
-  HIP_TRY(hipEventCreate(&ev1));
-  HIP_TRY(hipEventRecord(ev0, 0));
+  EventPair ev;
+  HIP_TRY(ev.create());
+  HIP_TRY(hipEventRecord(ev.ev0, 0));
   bool lds_done = false;
   if (try_lds) {
     hipLaunchKernelGGL(k_hashagg_lds, dim3(blocks), dim3(BG_BLOCK),
@@ -2214,53 +2300,39 @@ static int hashagg_impl(const bg_column* key_cols, int32_t nkeys,
                        aggs, reinterpret_cast<const u64*>(d_mask), n, cap - 1,
                        slot_data, err_flag);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ev1, 0));
-  HIP_TRY(hipEventSynchronize(ev1));
+  HIP_TRY(hipEventRecord(ev.ev1, 0));
+  HIP_TRY(hipEventSynchronize(ev.ev1));
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+  HIP_TRY(hipEventElapsedTime(&ms, ev.ev0, ev.ev1));
   g_last_kernel_ms = (double)ms;
-  HIP_TRY(hipEventDestroy(ev0));
-  HIP_TRY(hipEventDestroy(ev1));
 
   int err = 0;
   HIP_TRY(hipMemcpy(&err, err_flag, sizeof(int), hipMemcpyDeviceToHost));
-  if (err) {
-    (void)pool_release(slot_data);
-    (void)pool_release(err_flag);
+  if (err)
     return set_err(BG_ERR_INVALID, "bg_hashagg: table full (raise max_groups)");
-  }
 
   // compact occupied slots (ascending slot order — deterministic for a
   // fixed capacity) using the occupancy mask + stable compaction
   const int64_t nwords = ((int64_t)cap + 63) / 64;
-  u64* occ_mask;
-  uint32_t* sidx;
-  HIP_TRY(pool_malloc((void**)&occ_mask, sizeof(u64) * nwords));
-  HIP_TRY(pool_malloc((void**)&sidx, sizeof(uint32_t) * cap));
-  int oblocks = (int)bg_imin64((nwords * BG_WAVE + BG_BLOCK - 1) / BG_BLOCK,
-                               BG_MAX_BLOCKS);
-  if (oblocks == 0) oblocks = 1;
+  DevBuf<u64> occ_mask;
+  DevBuf<uint32_t> sidx;
+  HIP_TRY(occ_mask.alloc(nwords));
+  HIP_TRY(sidx.alloc(cap));
+  int oblocks = grid_for(nwords * BG_WAVE);
   hipLaunchKernelGGL(k_slot_occupancy, dim3(oblocks), dim3(BG_BLOCK), 0, 0,
                      slot_data, rec, (int64_t)cap, occ_mask);
   int64_t ngroups = 0;
-  int rc = bg_mask_to_indices(reinterpret_cast<const uint8_t*>(occ_mask),
+  int rc = bg_mask_to_indices(reinterpret_cast<const uint8_t*>(occ_mask.get()),
                               (int64_t)cap, sidx, &ngroups);
   if (rc != BG_OK) return rc;
-  if (ngroups > max_groups) {
+  if (ngroups > max_groups)
     // the open table (capacity 2*max_groups rounded up) absorbed more
     // distinct groups than the caller's OUTPUT buffers hold
-    (void)pool_release(slot_data);
-    (void)pool_release(err_flag);
-    (void)pool_release(occ_mask);
-    (void)pool_release(sidx);
     return set_err(BG_ERR_INVALID,
                    "bg_hashagg: table full (raise max_groups — more groups "
                    "than output capacity)");
-  }
 
-  int gblocks = (int)bg_imin64((ngroups + BG_BLOCK - 1) / BG_BLOCK,
-                               BG_MAX_BLOCKS);
-  if (gblocks == 0) gblocks = 1;
+  int gblocks = grid_for(ngroups);
   hipLaunchKernelGGL(k_hashagg_gather, dim3(gblocks), dim3(BG_BLOCK), 0, 0,
                      sidx, ngroups, slot_data, naggs, vmode, d_first_row,
                      reinterpret_cast<u64*>(d_counts_out),
@@ -2268,10 +2340,6 @@ static int hashagg_impl(const bg_column* key_cols, int32_t nkeys,
                      reinterpret_cast<u64*>(d_nncnt_out));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(pool_release(slot_data));
-  HIP_TRY(pool_release(err_flag));
-  HIP_TRY(pool_release(occ_mask));
-  HIP_TRY(pool_release(sidx));
   *out_ngroups = ngroups;
   return BG_OK;
 }
@@ -2338,8 +2406,7 @@ extern "C" int bg_project_dec128(int32_t op, const bg_column* a,
   REQUIRE_INIT();
   if (op <= 2 && b == nullptr)
     return set_err(BG_ERR_INVALID, "binary op needs column b");
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(n);
   const i128 lit = ((i128)lit_hi << 64) | (i128)(u128)(u64)lit_lo;
   hipLaunchKernelGGL(k_project_dec128, dim3(blocks), dim3(BG_BLOCK), 0, 0, op,
                      (const ulong2*)a->d_data,
@@ -2560,26 +2627,29 @@ __global__ void k_hist_trivial(const u64* hist, int64_t nchunks, int64_t n,
 // Stable radix passes over one or two u64 key words held in CURRENT
 // permutation order, via the fused digit+hist and digit+scatter+materialise
 // kernels above (no pids array, no separate rank/apply passes).
-static int radix_sort_passes(u64* d_key_words[2], int nwords, int64_t n,
-                             uint32_t* d_perm, int npasses_per_word) {
+// d_key_words are the caller's OWNERS: each scatter pass swaps them with
+// this function's spare buffers, so on return the caller holds whichever
+// buffers carry the sorted keys and the spares are released here — every
+// buffer exactly once, whoever ends up holding it.
+static int radix_sort_passes(DevBuf<u64> d_key_words[2], int nwords,
+                             int64_t n, uint32_t* d_perm,
+                             int npasses_per_word) {
   const int64_t nchunks = (n + PS_ROWS_PER_WAVE - 1) / PS_ROWS_PER_WAVE;
   const int64_t hist_len = 256 * (nchunks ? nchunks : 1);
-  u64* d_hist;
-  i64* d_start;
-  u64* d_nxt[2] = {nullptr, nullptr};
-  uint32_t* d_nxtperm;
-  HIP_TRY(pool_malloc((void**)&d_hist, sizeof(u64) * hist_len));
-  HIP_TRY(pool_malloc((void**)&d_start, sizeof(i64) * hist_len));
-  HIP_TRY(pool_malloc((void**)&d_nxtperm, sizeof(uint32_t) * (n ? n : 1)));
-  int* d_flag;
-  HIP_TRY(pool_malloc((void**)&d_flag, sizeof(int)));
-  for (int w = 0; w < nwords; ++w)
-    HIP_TRY(pool_malloc((void**)&d_nxt[w], sizeof(u64) * (n ? n : 1)));
+  DevBuf<u64> d_hist;
+  DevBuf<i64> d_start;
+  DevBuf<u64> d_nxt[2];
+  DevBuf<uint32_t> d_nxtperm;  // the other half of the perm ping-pong
+  HIP_TRY(d_hist.alloc(hist_len));
+  HIP_TRY(d_start.alloc(hist_len));
+  HIP_TRY(d_nxtperm.alloc(n));
+  DevBuf<int> d_flag;
+  HIP_TRY(d_flag.alloc(1));
+  for (int w = 0; w < nwords; ++w) HIP_TRY(d_nxt[w].alloc(n));
   const int waves_per_block = BG_BLOCK / BG_WAVE;
   const size_t lds_hist = (size_t)waves_per_block * 256 * sizeof(uint32_t);
   const size_t lds_scat = (size_t)waves_per_block * 256 * sizeof(i64);
-  int blocks = (int)bg_imin64(nchunks, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(nchunks, 1);
   int rc = BG_OK;
   const int total_passes = npasses_per_word * nwords;
   uint32_t* perm_cur = d_perm;
@@ -2618,16 +2688,8 @@ static int radix_sort_passes(u64* d_key_words[2], int nwords, int64_t n,
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { rc = set_hip_err(e, "radix scatter"); break; }
     // ping-pong
-    {
-      u64* t = d_key_words[word];
-      d_key_words[word] = d_nxt[word];
-      d_nxt[word] = t;
-    }
-    if (khi) {
-      u64* t = d_key_words[1];
-      d_key_words[1] = d_nxt[1];
-      d_nxt[1] = t;
-    }
+    d_key_words[word].swap(d_nxt[word]);
+    if (khi) d_key_words[1].swap(d_nxt[1]);
     uint32_t* tp = perm_cur;
     perm_cur = perm_nxt;
     perm_nxt = tp;
@@ -2637,13 +2699,6 @@ static int radix_sort_passes(u64* d_key_words[2], int nwords, int64_t n,
                                   hipMemcpyDeviceToDevice, 0);
     if (e != hipSuccess) rc = set_hip_err(e, "perm copy");
   }
-  // release whichever buffers are NOT the caller's perm; the swapped key
-  // buffers are re-adopted by the caller (bg_sort_rows)
-  (void)pool_release(d_hist);
-  (void)pool_release(d_start);
-  (void)pool_release(d_nxtperm);  // never d_perm: it is the caller's buffer
-  (void)pool_release(d_flag);
-  for (int w = 0; w < nwords; ++w) (void)pool_release(d_nxt[w]);
   return rc;
 }
 
@@ -2710,15 +2765,13 @@ static int sort_rows_impl(const bg_column* key_cols,
   REQUIRE_INIT();
   if (nkeys <= 0 || nkeys > BG_MAX_KEYS)
     return set_err(BG_ERR_INVALID, "nkeys out of range [1,4]");
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(n);
   hipLaunchKernelGGL(k_iota_u32, dim3(blocks), dim3(BG_BLOCK), 0, 0, d_perm, n);
-  u64* d_keyu[2];
-  u64* d_keyperm[2];
-  HIP_TRY(pool_malloc((void**)&d_keyu[0], sizeof(u64) * (n ? n : 1)));
-  HIP_TRY(pool_malloc((void**)&d_keyu[1], sizeof(u64) * (n ? n : 1)));
-  HIP_TRY(pool_malloc((void**)&d_keyperm[0], sizeof(u64) * (n ? n : 1)));
-  HIP_TRY(pool_malloc((void**)&d_keyperm[1], sizeof(u64) * (n ? n : 1)));
+  DevBuf<u64> d_keyu[2], d_keyperm[2];
+  HIP_TRY(d_keyu[0].alloc(n));
+  HIP_TRY(d_keyu[1].alloc(n));
+  HIP_TRY(d_keyperm[0].alloc(n));
+  HIP_TRY(d_keyperm[1].alloc(n));
   int rc = BG_OK;
   for (int c = nkeys - 1; c >= 0 && rc == BG_OK; --c) {
     int npasses, nwords;
@@ -2727,14 +2780,14 @@ static int sort_rows_impl(const bg_column* key_cols,
         hipLaunchKernelGGL(k_key_transform_i64, dim3(blocks), dim3(BG_BLOCK),
                            0, 0, (const int64_t*)key_cols[c].d_data,
                            key_cols[c].d_validity, n,
-                           descending[c], d_keyu[0]);
+                           descending[c], d_keyu[0].get());
         npasses = 8; nwords = 1;
         break;
       case BG_DT_FLOAT64:
         hipLaunchKernelGGL(k_key_transform_f64, dim3(blocks), dim3(BG_BLOCK),
                            0, 0, (const int64_t*)key_cols[c].d_data,
                            key_cols[c].d_validity, n,
-                           descending[c], d_keyu[0]);
+                           descending[c], d_keyu[0].get());
         npasses = 8; nwords = 1;
         break;
       case BG_DT_INT32:
@@ -2742,7 +2795,7 @@ static int sort_rows_impl(const bg_column* key_cols,
         hipLaunchKernelGGL(k_key_transform_i32, dim3(blocks), dim3(BG_BLOCK),
                            0, 0, (const int32_t*)key_cols[c].d_data,
                            key_cols[c].d_validity, n,
-                           descending[c], d_keyu[0]);
+                           descending[c], d_keyu[0].get());
         npasses = 4; nwords = 1;
         break;
       case BG_DT_DECIMAL128:
@@ -2750,7 +2803,8 @@ static int sort_rows_impl(const bg_column* key_cols,
                            dim3(BG_BLOCK), 0, 0,
                            (const ulong2*)key_cols[c].d_data,
                            key_cols[c].d_validity, n,
-                           descending[c], d_keyu[0], d_keyu[1]);
+                           descending[c], d_keyu[0].get(),
+                           d_keyu[1].get());
         npasses = 8; nwords = 2;
         break;
       case BG_DT_UTF8: {
@@ -2759,15 +2813,15 @@ static int sort_rows_impl(const bg_column* key_cols,
         // extracted in the CURRENT perm order (no separate permute)
         const uint8_t* d_data = (const uint8_t*)key_cols[c].d_data;
         const int32_t* d_offs = key_cols[c].d_offsets;
-        int* d_maxlen;
-        HIP_TRY(pool_malloc((void**)&d_maxlen, sizeof(int)));
+        DevBuf<int> d_maxlen;
+        HIP_TRY(d_maxlen.alloc(1));
         HIP_TRY(hipMemsetAsync(d_maxlen, 0, sizeof(int), 0));
         hipLaunchKernelGGL(k_utf8_maxlen, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                            d_offs, n, d_maxlen);
         int maxlen = 0;
         HIP_TRY(hipMemcpy(&maxlen, d_maxlen, sizeof(int),
                           hipMemcpyDeviceToHost));
-        (void)pool_release(d_maxlen);
+        d_maxlen.reset();
         if (maxlen > (1 << 20))
           return set_err(BG_ERR_INVALID, "utf8 sort keys > 1 MiB");
         const int64_t nch = ((int64_t)maxlen + 7) / 8;
@@ -2776,19 +2830,15 @@ static int sort_rows_impl(const bg_column* key_cols,
           hipLaunchKernelGGL(k_utf8_chunk_key, dim3(blocks), dim3(BG_BLOCK),
                              0, 0, d_data, d_offs, key_cols[c].d_validity,
                              d_perm, n, chunk,
-                             descending[c], d_keyperm[0]);
-          u64* words[2] = {d_keyperm[0], d_keyperm[1]};
-          rc = radix_sort_passes(words, 1, n, d_perm, 8);
-          d_keyperm[0] = words[0];
+                             descending[c], d_keyperm[0].get());
+          rc = radix_sort_passes(d_keyperm, 1, n, d_perm, 8);
         }
         if (rc == BG_OK && key_cols[c].d_validity) {
           hipLaunchKernelGGL(k_null_order_key, dim3(blocks), dim3(BG_BLOCK),
                              0, 0, key_cols[c].d_validity, d_perm, n,
                              nulls_first ? nulls_first[c] : descending[c],
-                             d_keyperm[0]);
-          u64* words[2] = {d_keyperm[0], d_keyperm[1]};
-          rc = radix_sort_passes(words, 1, n, d_perm, 1);
-          d_keyperm[0] = words[0];
+                             d_keyperm[0].get());
+          rc = radix_sort_passes(d_keyperm, 1, n, d_perm, 1);
         }
         continue;
       }
@@ -2798,15 +2848,10 @@ static int sort_rows_impl(const bg_column* key_cols,
         continue;
     }
     // bring the key stream into the CURRENT permutation order once
-    u64* words[2] = {d_keyperm[0], d_keyperm[1]};
     for (int w = 0; w < nwords; ++w)
       hipLaunchKernelGGL(k_permute_u64, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                         d_keyu[w], d_perm, n, d_keyperm[w]);
-    rc = radix_sort_passes(words, nwords, n, d_perm, npasses);
-    // radix passes ping-pong the key buffers: re-adopt whatever pointers
-    // ended up live so the release below frees each buffer exactly once
-    d_keyperm[0] = words[0];
-    if (nwords > 1) d_keyperm[1] = words[1];
+                         d_keyu[w].get(), d_perm, n, d_keyperm[w].get());
+    rc = radix_sort_passes(d_keyperm, nwords, n, d_perm, npasses);
     if (rc == BG_OK && key_cols[c].d_validity) {
       // null-ordering pass — the MOST significant criterion for this
       // key: SQL default NULLS LAST for ASC, NULLS FIRST for DESC
@@ -2814,16 +2859,10 @@ static int sort_rows_impl(const bg_column* key_cols,
       hipLaunchKernelGGL(k_null_order_key, dim3(blocks), dim3(BG_BLOCK),
                          0, 0, key_cols[c].d_validity, d_perm, n,
                          nulls_first ? nulls_first[c] : descending[c],
-                         d_keyperm[0]);
-      u64* words2[2] = {d_keyperm[0], d_keyperm[1]};
-      rc = radix_sort_passes(words2, 1, n, d_perm, 1);
-      d_keyperm[0] = words2[0];
+                         d_keyperm[0].get());
+      rc = radix_sort_passes(d_keyperm, 1, n, d_perm, 1);
     }
   }
-  (void)pool_release(d_keyu[0]);
-  (void)pool_release(d_keyu[1]);
-  (void)pool_release(d_keyperm[0]);
-  (void)pool_release(d_keyperm[1]);
   if (rc == BG_OK) HIP_TRY(hipGetLastError());
   return rc;
 }
@@ -2905,16 +2944,15 @@ extern "C" int bg_merge_join(const int64_t* d_build_sorted, int64_t nb,
                              int64_t* out_matches, uint32_t* d_out_probe,
                              uint32_t* d_out_build) {
   REQUIRE_INIT();
-  u64* d_counts;
-  int64_t* d_lbs;
-  i64* d_offs;
-  i64* d_total;
-  HIP_TRY(pool_malloc((void**)&d_counts, sizeof(u64) * (np ? np : 1)));
-  HIP_TRY(pool_malloc((void**)&d_lbs, sizeof(int64_t) * (np ? np : 1)));
-  HIP_TRY(pool_malloc((void**)&d_offs, sizeof(i64) * (np ? np : 1)));
-  HIP_TRY(pool_malloc((void**)&d_total, sizeof(i64)));
-  int blocks = (int)bg_imin64((np + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  DevBuf<u64> d_counts;
+  DevBuf<int64_t> d_lbs;
+  DevBuf<i64> d_offs;
+  DevBuf<i64> d_total;
+  HIP_TRY(d_counts.alloc(np));
+  HIP_TRY(d_lbs.alloc(np));
+  HIP_TRY(d_offs.alloc(np));
+  HIP_TRY(d_total.alloc(1));
+  int blocks = grid_for(np);
   hipLaunchKernelGGL(k_merge_count, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      d_build_sorted, nb, d_probe_sorted, np, d_counts, d_lbs);
   int rc = scan_exclusive_i64(d_counts, np, d_offs, d_total);
@@ -2931,10 +2969,6 @@ extern "C" int bg_merge_join(const int64_t* d_build_sorted, int64_t nb,
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) rc = set_hip_err(e, "merge fill");
   }
-  (void)pool_release(d_counts);
-  (void)pool_release(d_lbs);
-  (void)pool_release(d_offs);
-  (void)pool_release(d_total);
   if (rc == BG_OK) *out_matches = total;
   return rc;
 }
@@ -3890,45 +3924,46 @@ __global__ void k_snap_par_fill(const SnappyPage* __restrict__ pages,
   }
 }
 
-/* Decompress npages independent Snappy blocks.  pages: HOST array copied
- * internally; each entry's src/dst are DEVICE pointers.  out_lens (host,
- * npages): decompressed length or -1 on malformed input. */
-extern "C" int bg_snappy_decompress(const void* h_pages, int64_t npages,
-                                    int64_t* h_out_lens) {
-  REQUIRE_INIT();
-  if (npages <= 0) return BG_OK;
-  const SnappyPage* hp = (const SnappyPage*)h_pages;
-  std::vector<int64_t> base(npages + 1);
-  base[0] = 0;
-  for (int64_t p = 0; p < npages; ++p)
-    base[p + 1] = base[p] + hp[p].src_len / 2 + 2;
-  SnappyPage* d_pages;
-  int64_t* d_lens;
-  int64_t* d_base;
-  int64_t* d_counts;
-  SnapDesc* d_descs;
-  HIP_TRY(pool_malloc((void**)&d_pages, sizeof(SnappyPage) * npages));
-  HIP_TRY(pool_malloc((void**)&d_lens, sizeof(int64_t) * npages));
-  HIP_TRY(pool_malloc((void**)&d_base, sizeof(int64_t) * (npages + 1)));
-  HIP_TRY(pool_malloc((void**)&d_counts, sizeof(int64_t) * npages));
-  HIP_TRY(pool_malloc((void**)&d_descs, sizeof(SnapDesc) * base[npages]));
-  HIP_TRY(hipMemcpy(d_pages, h_pages, sizeof(SnappyPage) * npages,
-                    hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_base, base.data(), sizeof(int64_t) * (npages + 1),
-                    hipMemcpyHostToDevice));
-  const bool dbg = getenv("BG_SNAPPY_DEBUG") != nullptr;
-  double t_parse = 0, t_lit = 0, t_match = 0;
-  auto tick = [&]() -> double {
-    if (!dbg) return 0.0;
-    (void)hipDeviceSynchronize();
-    return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(
-               std::chrono::steady_clock::now().time_since_epoch())
-               .count() / 1e6;
-  };
-  double t0 = tick();
-  const int wpb1 = BG_BLOCK / BG_WAVE;  // parse waves per block
-  int blocks1 = (int)bg_imin64((npages + wpb1 - 1) / wpb1, BG_MAX_BLOCKS);
-  if (blocks1 == 0) blocks1 = 1;
+// ---- bg_snappy_decompress host side: route -> parse -> literals ->
+// replay -> matches, one static function per phase ----
+
+// device arrays every phase of one call shares
+struct SnapDev {
+  DevBuf<SnappyPage> pages;
+  DevBuf<int64_t> lens, base, counts;
+  DevBuf<SnapDesc> descs;
+};
+
+// the host-side routing decision of one call
+struct SnapRoute {
+  std::vector<SnapBigPage> bigs;       // pages for the segmented parse
+  std::vector<int32_t> seg_page;       // segment -> index into bigs
+  int64_t segsz = 0;                   // segment size this call
+  int64_t arr_total = 0;               // per-byte array elements over bigs
+  int64_t seg_total = 0;               // segments over bigs
+  std::vector<SnapBigPage> par_pages;  // pages replayed by list ranking
+};
+
+// BG_SNAPPY_DEBUG wall clock in ms (drains the device); 0 when disabled
+static double snap_tick(bool dbg) {
+  if (!dbg) return 0.0;
+  (void)hipDeviceSynchronize();
+  return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(
+             std::chrono::steady_clock::now().time_since_epoch())
+             .count() / 1e6;
+}
+
+static bool snap_is_big(const SnappyPage& pg) {
+  if (pg.src_len <= SNAPBIG_THRESHOLD) return false;
+  if (pg.dst_cap > 0 && (double)pg.src_len > 0.85 * (double)pg.dst_cap)
+    return false;
+  return true;
+}
+
+// Pure host step (no HIP call): which pages take the segmented parse and
+// which are replayed by list ranking.
+static SnapRoute snap_route(const SnappyPage* hp, int64_t npages) {
+  SnapRoute r;
   // giant pages (dict-fallback ~1 MB pages) go through the segmented
   // self-synchronizing parse; the wave chase handles the rest.  The
   // chase kernel still runs over ALL pages but exits immediately for big
@@ -3938,34 +3973,24 @@ extern "C" int bg_snappy_decompress(const void* h_pages, int64_t npages,
   // route to the segmented path: big AND element-dense.  Near-
   // incompressible pages are literal-dominated (few elements) and the
   // wave chase handles them at full rate.
-  auto is_big = [&](int64_t p) {
-    if (hp[p].src_len <= SNAPBIG_THRESHOLD) return false;
-    if (hp[p].dst_cap > 0 &&
-        (double)hp[p].src_len > 0.85 * (double)hp[p].dst_cap)
-      return false;
-    return true;
-  };
-  std::vector<SnapBigPage> bigs;
-  std::vector<int32_t> seg_page;
-  int64_t arr_total = 0, seg_total = 0;
   int64_t nbig_est = 0;
   for (int64_t p = 0; p < npages; ++p)
-    if (is_big(p)) ++nbig_est;
-  const int64_t segsz = nbig_est <= 768 ? SNAPBIG_SEG / 2 : SNAPBIG_SEG;
+    if (snap_is_big(hp[p])) ++nbig_est;
+  r.segsz = nbig_est <= 768 ? SNAPBIG_SEG / 2 : SNAPBIG_SEG;
   for (int64_t p = 0; p < npages; ++p) {
-    if (!is_big(p)) continue;
+    if (!snap_is_big(hp[p])) continue;
     SnapBigPage bp;
     bp.page_idx = p;
-    bp.arr_base = arr_total;
-    bp.seg_base = seg_total;
-    bp.nsegs = (hp[p].src_len + segsz - 1) / segsz;
-    bp.seg_sz = segsz;
+    bp.arr_base = r.arr_total;
+    bp.seg_base = r.seg_total;
+    bp.nsegs = (hp[p].src_len + r.segsz - 1) / r.segsz;
+    bp.seg_sz = r.segsz;
     bp.par_base = 0;
-    arr_total += hp[p].src_len;
+    r.arr_total += hp[p].src_len;
     for (int64_t k = 0; k < bp.nsegs; ++k)
-      seg_page.push_back((int32_t)bigs.size());
-    seg_total += bp.nsegs;
-    bigs.push_back(bp);
+      r.seg_page.push_back((int32_t)r.bigs.size());
+    r.seg_total += bp.nsegs;
+    r.bigs.push_back(bp);
   }
   // List-ranking replay routing — INDEPENDENT of the segmented-parse
   // routing above: replay cost is set by matches x chain depth, not by
@@ -3989,7 +4014,6 @@ extern "C" int bg_snappy_decompress(const void* h_pages, int64_t npages,
   //       2000: 55 vs 25 ms).  List-rank only when the count is low.
   // The combined set is processed in chunks of <= 4 GB of parent arrays
   // to bound replay memory.
-  std::vector<SnapBigPage> par_pages;
   bool caps_ok = true;
   int64_t class_b = 0;
   for (int64_t p = 0; p < npages; ++p) {
@@ -4004,194 +4028,289 @@ extern "C" int bg_snappy_decompress(const void* h_pages, int64_t npages,
     SnapBigPage pp{};
     pp.page_idx = p;
     pp.par_base = ratio < 0.15 ? -1 : 0;  // -1 marks class A for the cut
-    par_pages.push_back(pp);
+    r.par_pages.push_back(pp);
     if (pp.par_base == 0) ++class_b;
   }
   if (!caps_ok) {
-    par_pages.clear();
+    r.par_pages.clear();
   } else if (class_b > 768) {
     // keep only class A
     std::vector<SnapBigPage> keep;
-    for (auto& pp : par_pages)
+    for (auto& pp : r.par_pages)
       if (pp.par_base < 0) keep.push_back(pp);
-    par_pages.swap(keep);
+    r.par_pages.swap(keep);
   }
-  const bool use_parents = !par_pages.empty();
-  uint8_t* d_isbig = nullptr;
-  if (bigs.empty()) {
-    hipLaunchKernelGGL(k_snap_parse, dim3(blocks1), dim3(BG_BLOCK), 0, 0,
-                       d_pages, npages, d_descs, d_base, d_counts, d_lens);
-    HIP_TRY(hipGetLastError());
-  } else {
-    // small pages via the chase (on a compacted page list mapped back)
-    std::vector<SnappyPage> smalls;
-    std::vector<int64_t> small_map, small_base;
-    for (int64_t p = 0; p < npages; ++p) {
-      if (is_big(p)) continue;
-      smalls.push_back(hp[p]);
-      small_map.push_back(p);
-      small_base.push_back(base[p]);
-    }
-    if (!smalls.empty()) {
-      SnappyPage* d_small;
-      int64_t* d_small_base;
-      int64_t* d_small_counts;
-      int64_t* d_small_lens;
-      HIP_TRY(pool_malloc((void**)&d_small,
-                          sizeof(SnappyPage) * smalls.size()));
-      HIP_TRY(pool_malloc((void**)&d_small_base,
-                          sizeof(int64_t) * smalls.size()));
-      HIP_TRY(pool_malloc((void**)&d_small_counts,
-                          sizeof(int64_t) * smalls.size()));
-      HIP_TRY(pool_malloc((void**)&d_small_lens,
-                          sizeof(int64_t) * smalls.size()));
-      HIP_TRY(hipMemcpy(d_small, smalls.data(),
-                        sizeof(SnappyPage) * smalls.size(),
-                        hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(d_small_base, small_base.data(),
-                        sizeof(int64_t) * smalls.size(),
-                        hipMemcpyHostToDevice));
-      int sb = (int)bg_imin64(((int64_t)smalls.size() + wpb1 - 1) / wpb1,
-                              BG_MAX_BLOCKS);
-      if (sb == 0) sb = 1;
-      hipLaunchKernelGGL(k_snap_parse, dim3(sb), dim3(BG_BLOCK), 0, 0,
-                         d_small, (int64_t)smalls.size(), d_descs,
-                         d_small_base, d_small_counts, d_small_lens);
-      HIP_TRY(hipGetLastError());
-      // scatter counts/lens back to the full arrays
-      std::vector<int64_t> tmpc(smalls.size()), tmpl(smalls.size());
-      HIP_TRY(hipMemcpy(tmpc.data(), d_small_counts,
-                        sizeof(int64_t) * smalls.size(),
-                        hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(tmpl.data(), d_small_lens,
-                        sizeof(int64_t) * smalls.size(),
-                        hipMemcpyDeviceToHost));
-      std::vector<int64_t> full_c(npages, 0), full_l(npages, 0);
-      for (size_t i = 0; i < smalls.size(); ++i) {
-        full_c[small_map[i]] = tmpc[i];
-        full_l[small_map[i]] = tmpl[i];
-      }
-      HIP_TRY(hipMemcpy(d_counts, full_c.data(), sizeof(int64_t) * npages,
-                        hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(d_lens, full_l.data(), sizeof(int64_t) * npages,
-                        hipMemcpyHostToDevice));
-      (void)pool_release(d_small);
-      (void)pool_release(d_small_base);
-      (void)pool_release(d_small_counts);
-      (void)pool_release(d_small_lens);
-    }
-    // big pages: A (spec) -> B (resolve) -> C (emit)
-    SnapBigPage* d_bigs;
-    int32_t* d_seg_page;
-    uint16_t* d_next16;
-    uint32_t* d_cnt_pre;
-    uint32_t* d_out_pre;
-    uint32_t* d_seg_ct;
-    uint32_t* d_seg_ot;
-    int64_t* d_seg_exit;
-    int64_t* d_seg_entry;
-    int64_t* d_seg_nd;
-    int64_t* d_seg_di;
-    int64_t* d_page_hdr;
-    int64_t* d_page_ulen;
-    HIP_TRY(pool_malloc((void**)&d_bigs, sizeof(SnapBigPage) * bigs.size()));
-    HIP_TRY(pool_malloc((void**)&d_seg_page, sizeof(int32_t) * seg_total));
-    HIP_TRY(pool_malloc((void**)&d_next16, sizeof(uint16_t) * arr_total));
-    HIP_TRY(pool_malloc((void**)&d_cnt_pre, sizeof(uint32_t) * arr_total));
-    HIP_TRY(pool_malloc((void**)&d_out_pre, sizeof(uint32_t) * arr_total));
-    HIP_TRY(pool_malloc((void**)&d_seg_ct, sizeof(uint32_t) * seg_total));
-    HIP_TRY(pool_malloc((void**)&d_seg_ot, sizeof(uint32_t) * seg_total));
-    HIP_TRY(pool_malloc((void**)&d_seg_exit, sizeof(int64_t) * seg_total));
-    HIP_TRY(pool_malloc((void**)&d_seg_entry, sizeof(int64_t) * seg_total));
-    HIP_TRY(pool_malloc((void**)&d_seg_nd, sizeof(int64_t) * seg_total));
-    HIP_TRY(pool_malloc((void**)&d_seg_di, sizeof(int64_t) * seg_total));
-    HIP_TRY(pool_malloc((void**)&d_page_hdr, sizeof(int64_t) * bigs.size()));
-    HIP_TRY(pool_malloc((void**)&d_page_ulen, sizeof(int64_t) * bigs.size()));
-    HIP_TRY(hipMemcpy(d_bigs, bigs.data(), sizeof(SnapBigPage) * bigs.size(),
-                      hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_seg_page, seg_page.data(),
-                      sizeof(int32_t) * seg_total, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d_next16, 0, sizeof(uint16_t) * arr_total));
-    int ab = (int)bg_imin64((seg_total + BG_BLOCK - 1) / BG_BLOCK,
-                            BG_MAX_BLOCKS);
-    if (ab == 0) ab = 1;
-    unsigned long long* d_dbg = nullptr;
-    if (dbg) {
-      HIP_TRY(pool_malloc((void**)&d_dbg, 32));
-      HIP_TRY(hipMemset(d_dbg, 0, 32));
-    }
+  return r;
+}
 
-    double tb0 = tick();
-    hipLaunchKernelGGL(k_snapbig_spec, dim3(ab), dim3(BG_BLOCK), 0, 0,
-                       d_pages, d_bigs, d_seg_page, seg_total, d_dbg,
-                       d_next16,
-                       d_cnt_pre, d_out_pre, d_seg_ct, d_seg_ot, d_seg_exit,
-                       d_page_hdr, d_page_ulen);
+// Wave-chase parse of every page the segmented parse does not take:
+// directly over the full page list when there is no big page, otherwise on
+// a compacted list whose counts/lens are scattered back to the full arrays.
+static int snap_parse_small(const SnapDev& d, const SnappyPage* hp,
+                            const std::vector<int64_t>& base, int64_t npages,
+                            bool any_big) {
+  const int wpb1 = BG_BLOCK / BG_WAVE;  // parse waves per block
+  if (!any_big) {
+    int blocks1 = grid_for(npages, wpb1);
+    hipLaunchKernelGGL(k_snap_parse, dim3(blocks1), dim3(BG_BLOCK), 0, 0,
+                       d.pages.get(), npages, d.descs.get(), d.base.get(),
+                       d.counts.get(), d.lens.get());
     HIP_TRY(hipGetLastError());
-    double tb1 = tick();
-    int64_t* d_w_land;
-    int64_t* d_w_cnt;
-    int64_t* d_w_out;
-    int64_t* d_w_exit;
-    HIP_TRY(pool_malloc((void**)&d_w_land, sizeof(int64_t) * seg_total));
-    HIP_TRY(pool_malloc((void**)&d_w_cnt, sizeof(int64_t) * seg_total));
-    HIP_TRY(pool_malloc((void**)&d_w_out, sizeof(int64_t) * seg_total));
-    HIP_TRY(pool_malloc((void**)&d_w_exit, sizeof(int64_t) * seg_total));
-    hipLaunchKernelGGL(k_snapbig_walk, dim3(ab), dim3(BG_BLOCK), 0, 0,
-                       d_pages, d_bigs, d_seg_page, seg_total, d_next16,
-                       d_seg_exit, d_page_hdr, d_w_land, d_w_cnt, d_w_out,
-                       d_w_exit);
-    HIP_TRY(hipGetLastError());
-    double tb1b = tick();
-    int bb = (int)bg_imin64(((int64_t)bigs.size() + BG_BLOCK - 1) / BG_BLOCK,
-                            BG_MAX_BLOCKS);
-    if (bb == 0) bb = 1;
-    hipLaunchKernelGGL(k_snapbig_resolve, dim3(bb), dim3(BG_BLOCK), 0, 0,
-                       d_pages, d_bigs, (int64_t)bigs.size(), d_dbg, d_next16,
-                       d_cnt_pre, d_out_pre, d_seg_ct, d_seg_ot, d_seg_exit,
-                       d_page_hdr, d_page_ulen, d_w_land, d_w_cnt, d_w_out,
-                       d_w_exit, d_seg_entry, d_seg_nd,
-                       d_seg_di, d_counts, d_lens);
-    HIP_TRY(hipGetLastError());
-    (void)pool_release(d_w_land);
-    (void)pool_release(d_w_cnt);
-    (void)pool_release(d_w_out);
-    (void)pool_release(d_w_exit);
-    double tb2 = tick();
-    hipLaunchKernelGGL(k_snapbig_emit, dim3(ab), dim3(BG_BLOCK), 0, 0,
-                       d_pages, d_bigs, d_seg_page, seg_total, d_seg_entry,
-                       d_seg_nd, d_seg_di, d_page_ulen, d_descs, d_base,
-                       d_lens);
-    HIP_TRY(hipGetLastError());
-    if (dbg) {
-      double tb3 = tick();
-      unsigned long long hc[4] = {0, 0, 0, 0};
-      (void)hipMemcpy(hc, d_dbg, 32, hipMemcpyDeviceToHost);
-      (void)pool_release(d_dbg);
-      fprintf(stderr,
-              "[bg_snappy]   big: nseg=%lld spec=%.3fms walk=%.3fms "
-              "resolve=%.3fms emit=%.3fms seg_steps=%llu catchup=%llu "
-              "spec_elems=%llu spec_died=%llu\n",
-              (long long)seg_total, tb1 - tb0, tb1b - tb1, tb2 - tb1b,
-              tb3 - tb2, hc[0], hc[1], hc[2], hc[3]);
-    }
-    (void)pool_release(d_bigs);
-    (void)pool_release(d_seg_page);
-    (void)pool_release(d_next16);
-    (void)pool_release(d_cnt_pre);
-    (void)pool_release(d_out_pre);
-    (void)pool_release(d_seg_ct);
-    (void)pool_release(d_seg_ot);
-    (void)pool_release(d_seg_exit);
-    (void)pool_release(d_seg_entry);
-    (void)pool_release(d_seg_nd);
-    (void)pool_release(d_seg_di);
-    (void)pool_release(d_page_hdr);
-    (void)pool_release(d_page_ulen);
+    return BG_OK;
   }
-  double t1 = tick();
-  t_parse = t1 - t0;
-  // pass 2: chunk grid.y at 65535 pages
+  // small pages via the chase (on a compacted page list mapped back)
+  std::vector<SnappyPage> smalls;
+  std::vector<int64_t> small_map, small_base;
+  for (int64_t p = 0; p < npages; ++p) {
+    if (snap_is_big(hp[p])) continue;
+    smalls.push_back(hp[p]);
+    small_map.push_back(p);
+    small_base.push_back(base[p]);
+  }
+  if (smalls.empty()) return BG_OK;
+  const int64_t ns = (int64_t)smalls.size();
+  DevBuf<SnappyPage> d_small;
+  DevBuf<int64_t> d_small_base, d_small_counts, d_small_lens;
+  HIP_TRY(d_small.alloc(ns));
+  HIP_TRY(d_small_base.alloc(ns));
+  HIP_TRY(d_small_counts.alloc(ns));
+  HIP_TRY(d_small_lens.alloc(ns));
+  HIP_TRY(hipMemcpy(d_small, smalls.data(), sizeof(SnappyPage) * ns,
+                    hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_small_base, small_base.data(), sizeof(int64_t) * ns,
+                    hipMemcpyHostToDevice));
+  int sb = grid_for(ns, wpb1);
+  hipLaunchKernelGGL(k_snap_parse, dim3(sb), dim3(BG_BLOCK), 0, 0,
+                     d_small.get(), ns, d.descs.get(), d_small_base.get(),
+                     d_small_counts.get(), d_small_lens.get());
+  HIP_TRY(hipGetLastError());
+  // scatter counts/lens back to the full arrays
+  std::vector<int64_t> tmpc(ns), tmpl(ns);
+  HIP_TRY(hipMemcpy(tmpc.data(), d_small_counts, sizeof(int64_t) * ns,
+                    hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(tmpl.data(), d_small_lens, sizeof(int64_t) * ns,
+                    hipMemcpyDeviceToHost));
+  std::vector<int64_t> full_c(npages, 0), full_l(npages, 0);
+  for (int64_t i = 0; i < ns; ++i) {
+    full_c[small_map[i]] = tmpc[i];
+    full_l[small_map[i]] = tmpl[i];
+  }
+  HIP_TRY(hipMemcpy(d.counts, full_c.data(), sizeof(int64_t) * npages,
+                    hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d.lens, full_l.data(), sizeof(int64_t) * npages,
+                    hipMemcpyHostToDevice));
+  return BG_OK;
+}
+
+// Segmented self-synchronizing parse of the big pages:
+// A (spec) -> walk -> B (resolve) -> C (emit)
+static int snap_parse_segmented(const SnapDev& d, const SnapRoute& r,
+                                bool dbg) {
+  const int64_t nbig = (int64_t)r.bigs.size();
+  const int64_t seg_total = r.seg_total, arr_total = r.arr_total;
+  DevBuf<SnapBigPage> d_bigs;
+  DevBuf<int32_t> d_seg_page;
+  DevBuf<uint16_t> d_next16;
+  DevBuf<uint32_t> d_cnt_pre, d_out_pre, d_seg_ct, d_seg_ot;
+  DevBuf<int64_t> d_seg_exit, d_seg_entry, d_seg_nd, d_seg_di;
+  DevBuf<int64_t> d_page_hdr, d_page_ulen;
+  HIP_TRY(d_bigs.alloc(nbig));
+  HIP_TRY(d_seg_page.alloc(seg_total));
+  HIP_TRY(d_next16.alloc(arr_total));
+  HIP_TRY(d_cnt_pre.alloc(arr_total));
+  HIP_TRY(d_out_pre.alloc(arr_total));
+  HIP_TRY(d_seg_ct.alloc(seg_total));
+  HIP_TRY(d_seg_ot.alloc(seg_total));
+  HIP_TRY(d_seg_exit.alloc(seg_total));
+  HIP_TRY(d_seg_entry.alloc(seg_total));
+  HIP_TRY(d_seg_nd.alloc(seg_total));
+  HIP_TRY(d_seg_di.alloc(seg_total));
+  HIP_TRY(d_page_hdr.alloc(nbig));
+  HIP_TRY(d_page_ulen.alloc(nbig));
+  HIP_TRY(hipMemcpy(d_bigs, r.bigs.data(), sizeof(SnapBigPage) * nbig,
+                    hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_seg_page, r.seg_page.data(),
+                    sizeof(int32_t) * seg_total, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_next16, 0, sizeof(uint16_t) * arr_total));
+  int ab = grid_for(seg_total);
+  DevBuf<unsigned long long> d_dbg;  // 4 debug counters; null unless dbg
+  if (dbg) {
+    HIP_TRY(d_dbg.alloc(4));
+    HIP_TRY(hipMemset(d_dbg, 0, 32));
+  }
+
+  double tb0 = snap_tick(dbg);
+  hipLaunchKernelGGL(k_snapbig_spec, dim3(ab), dim3(BG_BLOCK), 0, 0,
+                     d.pages.get(), d_bigs.get(), d_seg_page.get(), seg_total,
+                     d_dbg.get(), d_next16.get(), d_cnt_pre.get(),
+                     d_out_pre.get(), d_seg_ct.get(), d_seg_ot.get(),
+                     d_seg_exit.get(), d_page_hdr.get(), d_page_ulen.get());
+  HIP_TRY(hipGetLastError());
+  double tb1 = snap_tick(dbg);
+  DevBuf<int64_t> d_w_land, d_w_cnt, d_w_out, d_w_exit;
+  HIP_TRY(d_w_land.alloc(seg_total));
+  HIP_TRY(d_w_cnt.alloc(seg_total));
+  HIP_TRY(d_w_out.alloc(seg_total));
+  HIP_TRY(d_w_exit.alloc(seg_total));
+  hipLaunchKernelGGL(k_snapbig_walk, dim3(ab), dim3(BG_BLOCK), 0, 0,
+                     d.pages.get(), d_bigs.get(), d_seg_page.get(), seg_total,
+                     d_next16.get(), d_seg_exit.get(), d_page_hdr.get(),
+                     d_w_land.get(), d_w_cnt.get(), d_w_out.get(),
+                     d_w_exit.get());
+  HIP_TRY(hipGetLastError());
+  double tb1b = snap_tick(dbg);
+  int bb = grid_for(nbig);
+  hipLaunchKernelGGL(k_snapbig_resolve, dim3(bb), dim3(BG_BLOCK), 0, 0,
+                     d.pages.get(), d_bigs.get(), nbig, d_dbg.get(),
+                     d_next16.get(), d_cnt_pre.get(), d_out_pre.get(),
+                     d_seg_ct.get(), d_seg_ot.get(), d_seg_exit.get(),
+                     d_page_hdr.get(), d_page_ulen.get(), d_w_land.get(),
+                     d_w_cnt.get(), d_w_out.get(), d_w_exit.get(),
+                     d_seg_entry.get(), d_seg_nd.get(), d_seg_di.get(),
+                     d.counts.get(), d.lens.get());
+  HIP_TRY(hipGetLastError());
+  // the walk outputs are dead after resolve: back to the pool before emit
+  d_w_land.reset();
+  d_w_cnt.reset();
+  d_w_out.reset();
+  d_w_exit.reset();
+  double tb2 = snap_tick(dbg);
+  hipLaunchKernelGGL(k_snapbig_emit, dim3(ab), dim3(BG_BLOCK), 0, 0,
+                     d.pages.get(), d_bigs.get(), d_seg_page.get(), seg_total,
+                     d_seg_entry.get(), d_seg_nd.get(), d_seg_di.get(),
+                     d_page_ulen.get(), d.descs.get(), d.base.get(),
+                     d.lens.get());
+  HIP_TRY(hipGetLastError());
+  if (dbg) {
+    double tb3 = snap_tick(dbg);
+    unsigned long long hc[4] = {0, 0, 0, 0};
+    (void)hipMemcpy(hc, d_dbg, 32, hipMemcpyDeviceToHost);
+    fprintf(stderr,
+            "[bg_snappy]   big: nseg=%lld spec=%.3fms walk=%.3fms "
+            "resolve=%.3fms emit=%.3fms seg_steps=%llu catchup=%llu "
+            "spec_elems=%llu spec_died=%llu\n",
+            (long long)seg_total, tb1 - tb0, tb1b - tb1, tb2 - tb1b,
+            tb3 - tb2, hc[0], hc[1], hc[2], hc[3]);
+  }
+  return BG_OK;
+}
+
+// List-ranking replay of par_pages (parents are built here, after the
+// literal roots have landed), in chunks of <= 4 GB of parent arrays:
+// init, scatter, up to 20 doubling rounds, fill.
+static int snap_replay_listrank(const SnapDev& d, const SnappyPage* hp,
+                                const std::vector<SnapBigPage>& par_pages,
+                                bool dbg, int* par_rounds) {
+  DevBuf<int> d_changed;
+  HIP_TRY(d_changed.alloc(1));
+  const int64_t CHUNK_ELEMS = ((int64_t)4 << 30) / sizeof(uint32_t);
+  const int pb = 1024;  // multiple of 8: page->XCD swizzle
+  double tp_init = 0, tp_scat = 0, tp_dbl = 0, tp_fill = 0;
+  size_t ci = 0;
+  while (ci < par_pages.size()) {
+    std::vector<SnapBigPage> chunk;
+    int64_t elems = 0;
+    while (ci < par_pages.size()) {
+      const int64_t cap = hp[par_pages[ci].page_idx].dst_cap;
+      if (!chunk.empty() && elems + cap > CHUNK_ELEMS) break;
+      SnapBigPage pp = par_pages[ci];
+      pp.par_base = elems;
+      elems += cap;
+      chunk.push_back(pp);
+      ++ci;
+    }
+    const int64_t npar = (int64_t)chunk.size();
+    DevBuf<SnapBigPage> d_parp;  // per chunk: released at the end of each turn
+    DevBuf<uint32_t> d_par;
+    HIP_TRY(d_parp.alloc(npar));
+    // (a fallback to the serial replay when this fails goes here)
+    HIP_TRY(d_par.alloc(elems));
+    HIP_TRY(hipMemcpy(d_parp, chunk.data(), sizeof(SnapBigPage) * npar,
+                      hipMemcpyHostToDevice));
+    double tp0 = snap_tick(dbg);
+    hipLaunchKernelGGL(k_snap_par_init, dim3(pb), dim3(BG_BLOCK), 0, 0,
+                       d_parp.get(), npar, d.lens.get(), d_par.get());
+    HIP_TRY(hipGetLastError());
+    double tp1 = snap_tick(dbg);
+    for (int64_t b0 = 0; b0 < npar; b0 += 65535) {
+      uint32_t ny = (uint32_t)bg_imin64(npar - b0, 65535);
+      hipLaunchKernelGGL(k_snap_par_scatter, dim3(64, ny), dim3(BG_BLOCK), 0,
+                         0, d.descs.get(), d.base.get(), d.counts.get(),
+                         d_parp.get(), b0, d.lens.get(), d_par.get());
+      HIP_TRY(hipGetLastError());
+    }
+    double tp2 = snap_tick(dbg);
+    // jump-4 doubling: parents strictly decrease (validated at parse),
+    // so convergence is guaranteed; x4 path compression per round
+    for (int round = 0; round < 20; ++round) {
+      HIP_TRY(hipMemset(d_changed, 0, sizeof(int)));
+      hipLaunchKernelGGL(k_snap_par_double, dim3(pb), dim3(BG_BLOCK), 0, 0,
+                         d_parp.get(), npar, d.lens.get(), d_par.get(),
+                         d_changed.get());
+      HIP_TRY(hipGetLastError());
+      int h_changed = 0;
+      HIP_TRY(hipMemcpy(&h_changed, d_changed, sizeof(int),
+                        hipMemcpyDeviceToHost));
+      ++*par_rounds;
+      if (!h_changed) break;
+    }
+    double tp3 = snap_tick(dbg);
+    hipLaunchKernelGGL(k_snap_par_fill, dim3(pb), dim3(BG_BLOCK), 0, 0,
+                       d.pages.get(), d_parp.get(), npar, d.lens.get(),
+                       d_par.get());
+    HIP_TRY(hipGetLastError());
+    d_parp.reset();
+    d_par.reset();
+    if (dbg) {
+      double tp4 = snap_tick(dbg);
+      tp_init += tp1 - tp0;
+      tp_scat += tp2 - tp1;
+      tp_dbl += tp3 - tp2;
+      tp_fill += tp4 - tp3;
+    }
+  }
+  if (dbg)
+    fprintf(stderr,
+            "[bg_snappy]   par: npar=%lld init=%.3fms scatter=%.3fms "
+            "double=%.3fms fill=%.3fms\n",
+            (long long)par_pages.size(), tp_init, tp_scat, tp_dbl, tp_fill);
+  return BG_OK;
+}
+
+/* Decompress npages independent Snappy blocks.  pages: HOST array copied
+ * internally; each entry's src/dst are DEVICE pointers.  out_lens (host,
+ * npages): decompressed length or -1 on malformed input. */
+extern "C" int bg_snappy_decompress(const void* h_pages, int64_t npages,
+                                    int64_t* h_out_lens) {
+  REQUIRE_INIT();
+  if (npages <= 0) return BG_OK;
+  const SnappyPage* hp = (const SnappyPage*)h_pages;
+  std::vector<int64_t> base(npages + 1);
+  base[0] = 0;
+  for (int64_t p = 0; p < npages; ++p)
+    base[p + 1] = base[p] + hp[p].src_len / 2 + 2;
+  SnapDev d;
+  HIP_TRY(d.pages.alloc(npages));
+  HIP_TRY(d.lens.alloc(npages));
+  HIP_TRY(d.base.alloc(npages + 1));
+  HIP_TRY(d.counts.alloc(npages));
+  HIP_TRY(d.descs.alloc(base[npages]));
+  HIP_TRY(hipMemcpy(d.pages, h_pages, sizeof(SnappyPage) * npages,
+                    hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d.base, base.data(), sizeof(int64_t) * (npages + 1),
+                    hipMemcpyHostToDevice));
+  const bool dbg = getenv("BG_SNAPPY_DEBUG") != nullptr;
+  const SnapRoute route = snap_route(hp, npages);
+
+  // parse: the wave chase for small pages, the segmented parse for big ones
+  double t0 = snap_tick(dbg);
+  const bool any_big = !route.bigs.empty();
+  if (int rc = snap_parse_small(d, hp, base, npages, any_big)) return rc;
+  if (any_big)
+    if (int rc = snap_parse_segmented(d, route, dbg)) return rc;
+  double t1 = snap_tick(dbg);
+
+  // literals — pass 2: chunk grid.y at 65535 pages
   const int waves_per_block = BG_BLOCK / BG_WAVE;
   // enough x-blocks to spread big pages' literal lists over the chip
   int xb = (int)bg_imin64(
@@ -4199,120 +4318,43 @@ extern "C" int bg_snappy_decompress(const void* h_pages, int64_t npages,
   for (int64_t p0 = 0; p0 < npages; p0 += 65535) {
     uint32_t ny = (uint32_t)bg_imin64(npages - p0, 65535);
     hipLaunchKernelGGL(k_snap_literals, dim3((uint32_t)xb, ny),
-                       dim3(BG_BLOCK), 0, 0, d_pages, p0, d_descs, d_base,
-                       d_counts);
+                       dim3(BG_BLOCK), 0, 0, d.pages.get(), p0,
+                       d.descs.get(), d.base.get(), d.counts.get());
     HIP_TRY(hipGetLastError());
   }
-  double t2 = tick();
-  t_lit = t2 - t1;
-  // big pages: list-ranking replay (parents were NOT built yet — all
-  // phases run here, after the literal roots have landed)
+  double t2 = snap_tick(dbg);
+
+  // replay: list ranking for the routed pages; k_snap_matches skips them
   double t_par = 0;
   int par_rounds = 0;
-  if (use_parents) {
+  DevBuf<uint8_t> d_isbig;  // stays null when no page is list-ranked
+  if (!route.par_pages.empty()) {
     std::vector<uint8_t> isbig(npages, 0);
-    for (auto& pp : par_pages) isbig[pp.page_idx] = 1;
-    HIP_TRY(pool_malloc((void**)&d_isbig, npages));
-    HIP_TRY(hipMemcpy(d_isbig, isbig.data(), npages,
-                      hipMemcpyHostToDevice));
-    int* d_changed;
-    HIP_TRY(pool_malloc((void**)&d_changed, sizeof(int)));
-    const int64_t CHUNK_ELEMS = ((int64_t)4 << 30) / sizeof(uint32_t);
-    const int pb = 1024;  // multiple of 8: page->XCD swizzle
-    double tp_init = 0, tp_scat = 0, tp_dbl = 0, tp_fill = 0;
-    size_t ci = 0;
-    while (ci < par_pages.size()) {
-      std::vector<SnapBigPage> chunk;
-      int64_t elems = 0;
-      while (ci < par_pages.size()) {
-        const int64_t cap = hp[par_pages[ci].page_idx].dst_cap;
-        if (!chunk.empty() && elems + cap > CHUNK_ELEMS) break;
-        SnapBigPage pp = par_pages[ci];
-        pp.par_base = elems;
-        elems += cap;
-        chunk.push_back(pp);
-        ++ci;
-      }
-      const int64_t npar = (int64_t)chunk.size();
-      SnapBigPage* d_parp;
-      uint32_t* d_par;
-      HIP_TRY(pool_malloc((void**)&d_parp, sizeof(SnapBigPage) * npar));
-      HIP_TRY(pool_malloc((void**)&d_par, sizeof(uint32_t) * elems));
-      HIP_TRY(hipMemcpy(d_parp, chunk.data(), sizeof(SnapBigPage) * npar,
-                        hipMemcpyHostToDevice));
-      double tp0 = tick();
-      hipLaunchKernelGGL(k_snap_par_init, dim3(pb), dim3(BG_BLOCK), 0, 0,
-                         d_parp, npar, d_lens, d_par);
-      HIP_TRY(hipGetLastError());
-      double tp1 = tick();
-      for (int64_t b0 = 0; b0 < npar; b0 += 65535) {
-        uint32_t ny = (uint32_t)bg_imin64(npar - b0, 65535);
-        hipLaunchKernelGGL(k_snap_par_scatter, dim3(64, ny),
-                           dim3(BG_BLOCK), 0, 0, d_descs, d_base, d_counts,
-                           d_parp, b0, d_lens, d_par);
-        HIP_TRY(hipGetLastError());
-      }
-      double tp2 = tick();
-      // jump-4 doubling: parents strictly decrease (validated at parse),
-      // so convergence is guaranteed; x4 path compression per round
-      for (int round = 0; round < 20; ++round) {
-        HIP_TRY(hipMemset(d_changed, 0, sizeof(int)));
-        hipLaunchKernelGGL(k_snap_par_double, dim3(pb), dim3(BG_BLOCK), 0,
-                           0, d_parp, npar, d_lens, d_par, d_changed);
-        HIP_TRY(hipGetLastError());
-        int h_changed = 0;
-        HIP_TRY(hipMemcpy(&h_changed, d_changed, sizeof(int),
-                          hipMemcpyDeviceToHost));
-        ++par_rounds;
-        if (!h_changed) break;
-      }
-      double tp3 = tick();
-      hipLaunchKernelGGL(k_snap_par_fill, dim3(pb), dim3(BG_BLOCK), 0, 0,
-                         d_pages, d_parp, npar, d_lens, d_par);
-      HIP_TRY(hipGetLastError());
-      (void)pool_release(d_parp);
-      (void)pool_release(d_par);
-      if (dbg) {
-        double tp4 = tick();
-        tp_init += tp1 - tp0;
-        tp_scat += tp2 - tp1;
-        tp_dbl += tp3 - tp2;
-        tp_fill += tp4 - tp3;
-      }
-    }
-    (void)pool_release(d_changed);
-    if (dbg) {
-      t_par = tick() - t2;
-      fprintf(stderr,
-              "[bg_snappy]   par: npar=%lld init=%.3fms scatter=%.3fms "
-              "double=%.3fms fill=%.3fms\n",
-              (long long)par_pages.size(), tp_init, tp_scat, tp_dbl,
-              tp_fill);
-    }
+    for (auto& pp : route.par_pages) isbig[pp.page_idx] = 1;
+    HIP_TRY(d_isbig.alloc(npages));
+    HIP_TRY(hipMemcpy(d_isbig, isbig.data(), npages, hipMemcpyHostToDevice));
+    if (int rc = snap_replay_listrank(d, hp, route.par_pages, dbg,
+                                      &par_rounds))
+      return rc;
+    if (dbg) t_par = snap_tick(dbg) - t2;
   }
-  double t2b = tick();
-  int blocks3 = (int)bg_imin64(
-      (npages + waves_per_block - 1) / waves_per_block, BG_MAX_BLOCKS);
-  if (blocks3 == 0) blocks3 = 1;
+
+  // matches: the serial in-order replay of every other page
+  double t2b = snap_tick(dbg);
+  int blocks3 = grid_for(npages, waves_per_block);
   hipLaunchKernelGGL(k_snap_matches, dim3(blocks3), dim3(BG_BLOCK), 0, 0,
-                     d_pages, npages, d_descs, d_base, d_counts, d_isbig);
+                     d.pages.get(), npages, d.descs.get(), d.base.get(),
+                     d.counts.get(), d_isbig.get());
   HIP_TRY(hipGetLastError());
-  if (dbg) {
-    t_match = tick() - t2b;
+  if (dbg)
     fprintf(stderr,
             "[bg_snappy] npages=%lld parse=%.3fms literals=%.3fms "
             "par=%.3fms(rounds=%d) matches=%.3fms\n",
-            (long long)npages, t_parse, t_lit, t_par, par_rounds + 1,
-            t_match);
-  }
-  if (d_isbig) (void)pool_release(d_isbig);
-  HIP_TRY(hipMemcpy(h_out_lens, d_lens, sizeof(int64_t) * npages,
+            (long long)npages, t1 - t0, t2 - t1, t_par, par_rounds + 1,
+            snap_tick(dbg) - t2b);
+  d_isbig.reset();
+  HIP_TRY(hipMemcpy(h_out_lens, d.lens, sizeof(int64_t) * npages,
                     hipMemcpyDeviceToHost));
-  (void)pool_release(d_pages);
-  (void)pool_release(d_lens);
-  (void)pool_release(d_base);
-  (void)pool_release(d_counts);
-  (void)pool_release(d_descs);
   return BG_OK;
 }
 
@@ -4444,8 +4486,8 @@ extern "C" int bg_page_extract(const void* d_page, int64_t page_len,
                                int64_t nvals, int64_t src_esz,
                                int32_t has_def, int32_t flba_reverse) {
   REQUIRE_INIT();
-  int* d_err;
-  HIP_TRY(pool_malloc((void**)&d_err, sizeof(int)));
+  DevBuf<int> d_err;
+  HIP_TRY(d_err.alloc(1));
   HIP_TRY(hipMemset(d_err, 0, sizeof(int)));
   int blocks = (int)bg_imin64((nvals * src_esz + BG_BLOCK - 1) / BG_BLOCK, 512);
   if (blocks == 0) blocks = 1;
@@ -4456,7 +4498,6 @@ extern "C" int bg_page_extract(const void* d_page, int64_t page_len,
   HIP_TRY(hipGetLastError());
   int err = 0;
   HIP_TRY(hipMemcpy(&err, d_err, sizeof(int), hipMemcpyDeviceToHost));
-  (void)pool_release(d_err);
   if (err)
     return set_err(BG_ERR_UNSUPPORTED,
                    "bg_page_extract: page carries nulls or malformed def "
@@ -4657,8 +4698,8 @@ extern "C" int bg_dict_indices(const void* d_page, int64_t page_len,
                                int64_t nvals, int32_t has_def,
                                uint32_t* d_out_idx) {
   REQUIRE_INIT();
-  int* d_err;
-  HIP_TRY(pool_malloc((void**)&d_err, sizeof(int)));
+  DevBuf<int> d_err;
+  HIP_TRY(d_err.alloc(1));
   HIP_TRY(hipMemset(d_err, 0, sizeof(int)));
   hipLaunchKernelGGL(k_dict_indices, dim3(1), dim3(64), 0, 0,
                      (const uint8_t*)d_page, page_len, nvals, has_def,
@@ -4666,7 +4707,6 @@ extern "C" int bg_dict_indices(const void* d_page, int64_t page_len,
   HIP_TRY(hipGetLastError());
   int err = 0;
   HIP_TRY(hipMemcpy(&err, d_err, sizeof(int), hipMemcpyDeviceToHost));
-  (void)pool_release(d_err);
   if (err == 2)
     return set_err(BG_ERR_UNSUPPORTED, "bg_dict_indices: nulls (later round)");
   if (err)
@@ -4767,25 +4807,11 @@ __global__ void k_def_levels_batch(const DefLevelsJob* jobs, int64_t njobs,
 
 extern "C" int bg_def_levels_batch(const void* h_jobs, int64_t njobs) {
   REQUIRE_INIT();
-  DefLevelsJob* d_jobs;
-  int* d_err;
-  HIP_TRY(pool_malloc((void**)&d_jobs,
-                      sizeof(DefLevelsJob) * (njobs ? njobs : 1)));
-  HIP_TRY(pool_malloc((void**)&d_err, sizeof(int)));
-  HIP_TRY(hipMemset(d_err, 0, sizeof(int)));
-  HIP_TRY(hipMemcpy(d_jobs, h_jobs, sizeof(DefLevelsJob) * njobs,
-                    hipMemcpyHostToDevice));
-  const int waves_per_block = BG_BLOCK / BG_WAVE;
-  int blocks = (int)bg_imin64((njobs + waves_per_block - 1) / waves_per_block,
-                              BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
-  hipLaunchKernelGGL(k_def_levels_batch, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                     d_jobs, njobs, d_err);
-  HIP_TRY(hipGetLastError());
   int err = 0;
-  HIP_TRY(hipMemcpy(&err, d_err, sizeof(int), hipMemcpyDeviceToHost));
-  (void)pool_release(d_jobs);
-  (void)pool_release(d_err);
+  if (int rc = run_job_batch<DefLevelsJob>(
+          k_def_levels_batch, h_jobs, njobs,
+          grid_for(njobs, BG_BLOCK / BG_WAVE), &err))
+    return rc;
   if (err)
     return set_err(BG_ERR_INVALID, "bg_def_levels_batch: malformed levels");
   return BG_OK;
@@ -4994,24 +5020,11 @@ extern "C" int bg_list_levels_batch(const void* h_jobs, int64_t njobs,
                                     int32_t pass) {
   REQUIRE_INIT();
   if (njobs <= 0) return BG_OK;
-  ListLevelsJob* d_jobs;
-  int* d_err;
-  HIP_TRY(pool_malloc((void**)&d_jobs, sizeof(ListLevelsJob) * njobs));
-  HIP_TRY(pool_malloc((void**)&d_err, sizeof(int)));
-  HIP_TRY(hipMemset(d_err, 0, sizeof(int)));
-  HIP_TRY(hipMemcpy(d_jobs, h_jobs, sizeof(ListLevelsJob) * njobs,
-                    hipMemcpyHostToDevice));
-  const int waves_per_block = BG_BLOCK / BG_WAVE;
-  int blocks = (int)bg_imin64((njobs + waves_per_block - 1) / waves_per_block,
-                              BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
-  hipLaunchKernelGGL(k_list_levels_batch, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                     d_jobs, njobs, (int)pass, d_err);
-  HIP_TRY(hipGetLastError());
   int err = 0;
-  HIP_TRY(hipMemcpy(&err, d_err, sizeof(int), hipMemcpyDeviceToHost));
-  (void)pool_release(d_jobs);
-  (void)pool_release(d_err);
+  if (int rc = run_job_batch<ListLevelsJob>(
+          k_list_levels_batch, h_jobs, njobs,
+          grid_for(njobs, BG_BLOCK / BG_WAVE), &err, (int)pass))
+    return rc;
   if (err == 5)
     return set_err(BG_ERR_UNSUPPORTED,
                    "bg_list_levels_batch: row spans pages");
@@ -5311,25 +5324,11 @@ __global__ void k_delta_ba_batch(const DeltaBaJob* jobs, int64_t njobs,
 extern "C" int bg_delta_ba_batch(const void* h_jobs, int64_t njobs,
                                  int32_t pass) {
   REQUIRE_INIT();
-  DeltaBaJob* d_jobs;
-  int* d_err;
-  HIP_TRY(pool_malloc((void**)&d_jobs,
-                      sizeof(DeltaBaJob) * (njobs ? njobs : 1)));
-  HIP_TRY(pool_malloc((void**)&d_err, sizeof(int)));
-  HIP_TRY(hipMemset(d_err, 0, sizeof(int)));
-  HIP_TRY(hipMemcpy(d_jobs, h_jobs, sizeof(DeltaBaJob) * njobs,
-                    hipMemcpyHostToDevice));
-  const int waves_per_block = BG_BLOCK / BG_WAVE;
-  int blocks = (int)bg_imin64((njobs + waves_per_block - 1) / waves_per_block,
-                              BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
-  hipLaunchKernelGGL(k_delta_ba_batch, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                     d_jobs, njobs, (int)pass, d_err);
-  HIP_TRY(hipGetLastError());
   int err = 0;
-  HIP_TRY(hipMemcpy(&err, d_err, sizeof(int), hipMemcpyDeviceToHost));
-  (void)pool_release(d_jobs);
-  (void)pool_release(d_err);
+  if (int rc = run_job_batch<DeltaBaJob>(
+          k_delta_ba_batch, h_jobs, njobs,
+          grid_for(njobs, BG_BLOCK / BG_WAVE), &err, (int)pass))
+    return rc;
   if (err)
     return set_err(BG_ERR_INVALID, "bg_delta_ba_batch: malformed page");
   return BG_OK;
@@ -5346,25 +5345,11 @@ __global__ void k_delta_bp_batch(const DeltaBpJob* jobs, int64_t njobs,
 
 extern "C" int bg_delta_bp_batch(const void* h_jobs, int64_t njobs) {
   REQUIRE_INIT();
-  DeltaBpJob* d_jobs;
-  int* d_err;
-  HIP_TRY(pool_malloc((void**)&d_jobs,
-                      sizeof(DeltaBpJob) * (njobs ? njobs : 1)));
-  HIP_TRY(pool_malloc((void**)&d_err, sizeof(int)));
-  HIP_TRY(hipMemset(d_err, 0, sizeof(int)));
-  HIP_TRY(hipMemcpy(d_jobs, h_jobs, sizeof(DeltaBpJob) * njobs,
-                    hipMemcpyHostToDevice));
-  const int waves_per_block = BG_BLOCK / BG_WAVE;
-  int blocks = (int)bg_imin64((njobs + waves_per_block - 1) / waves_per_block,
-                              BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
-  hipLaunchKernelGGL(k_delta_bp_batch, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                     d_jobs, njobs, d_err);
-  HIP_TRY(hipGetLastError());
   int err = 0;
-  HIP_TRY(hipMemcpy(&err, d_err, sizeof(int), hipMemcpyDeviceToHost));
-  (void)pool_release(d_jobs);
-  (void)pool_release(d_err);
+  if (int rc = run_job_batch<DeltaBpJob>(
+          k_delta_bp_batch, h_jobs, njobs,
+          grid_for(njobs, BG_BLOCK / BG_WAVE), &err))
+    return rc;
   if (err)
     return set_err(BG_ERR_INVALID, "bg_delta_bp_batch: malformed page");
   return BG_OK;
@@ -5432,24 +5417,11 @@ __global__ void k_ba_extract_batch(const BaPageJob* jobs, int64_t njobs,
 
 extern "C" int bg_ba_extract_batch(const void* h_jobs, int64_t njobs) {
   REQUIRE_INIT();
-  BaPageJob* d_jobs;
-  int* d_err;
-  HIP_TRY(pool_malloc((void**)&d_jobs, sizeof(BaPageJob) * (njobs ? njobs : 1)));
-  HIP_TRY(pool_malloc((void**)&d_err, sizeof(int)));
-  HIP_TRY(hipMemset(d_err, 0, sizeof(int)));
-  HIP_TRY(hipMemcpy(d_jobs, h_jobs, sizeof(BaPageJob) * njobs,
-                    hipMemcpyHostToDevice));
-  const int waves_per_block = BG_BLOCK / BG_WAVE;
-  int blocks = (int)bg_imin64((njobs + waves_per_block - 1) / waves_per_block,
-                              BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
-  hipLaunchKernelGGL(k_ba_extract_batch, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                     d_jobs, njobs, d_err);
-  HIP_TRY(hipGetLastError());
   int err = 0;
-  HIP_TRY(hipMemcpy(&err, d_err, sizeof(int), hipMemcpyDeviceToHost));
-  (void)pool_release(d_jobs);
-  (void)pool_release(d_err);
+  if (int rc = run_job_batch<BaPageJob>(
+          k_ba_extract_batch, h_jobs, njobs,
+          grid_for(njobs, BG_BLOCK / BG_WAVE), &err))
+    return rc;
   if (err)
     return set_err(BG_ERR_INVALID, "bg_ba_extract_batch: malformed page");
   return BG_OK;
@@ -5480,8 +5452,7 @@ extern "C" int bg_ba_from_dict(const uint32_t* d_idx, const int32_t* d_doffs,
                                int64_t n, int64_t* d_lens_out,
                                int64_t* d_srcaddr_out) {
   REQUIRE_INIT();
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(n);
   hipLaunchKernelGGL(k_ba_from_dict, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      d_idx, d_doffs, (const uint8_t*)d_ddata, d_vidx, n,
                      d_lens_out, d_srcaddr_out);
@@ -5509,10 +5480,10 @@ extern "C" int bg_ba_materialize(const int64_t* d_lens,
                                  uint8_t* d_data /* total bytes */,
                                  int64_t data_cap, int64_t* out_total) {
   REQUIRE_INIT();
-  i64* d_offs64;
-  i64* d_total;
-  HIP_TRY(pool_malloc((void**)&d_offs64, sizeof(i64) * (n + 1)));
-  HIP_TRY(pool_malloc((void**)&d_total, sizeof(i64)));
+  DevBuf<i64> d_offs64;
+  DevBuf<i64> d_total;
+  HIP_TRY(d_offs64.alloc(n + 1));
+  HIP_TRY(d_total.alloc(1));
   {
     int rc = scan_exclusive_i64((const u64*)d_lens, n, d_offs64, d_total);
     if (rc != BG_OK) return rc;
@@ -5520,29 +5491,21 @@ extern "C" int bg_ba_materialize(const int64_t* d_lens,
   i64 total = 0;
   HIP_TRY(hipMemcpy(&total, d_total, sizeof(i64), hipMemcpyDeviceToHost));
   if (d_data == nullptr) {  // dry-run: size query only
-    (void)pool_release(d_offs64);
-    (void)pool_release(d_total);
     *out_total = total;
     return BG_OK;
   }
-  if (total > data_cap || total > 0x7fffffffLL) {
-    (void)pool_release(d_offs64);
-    (void)pool_release(d_total);
+  if (total > data_cap || total > 0x7fffffffLL)
     return set_err(BG_ERR_INVALID, "bg_ba_materialize: data_cap/2GiB bound");
-  }
   HIP_TRY(hipMemcpy(d_offs64 + n, &total, sizeof(i64),
                     hipMemcpyHostToDevice));
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(n);
   hipLaunchKernelGGL(k_ba_copy, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                     d_srcaddr, (const int64_t*)d_offs64, d_offs32, d_data,
+                     d_srcaddr, (const int64_t*)d_offs64.get(), d_offs32, d_data,
                      n);
   HIP_TRY(hipGetLastError());
   const int32_t t32 = (int32_t)total;
   HIP_TRY(hipMemcpy(d_offs32 + n, &t32, sizeof(int32_t),
                     hipMemcpyHostToDevice));
-  (void)pool_release(d_offs64);
-  (void)pool_release(d_total);
   *out_total = total;
   return BG_OK;
 }
@@ -5612,23 +5575,11 @@ __global__ void k_bss_batch(const PageExtractJob* jobs, int64_t njobs,
 
 extern "C" int bg_bss_batch(const void* h_jobs, int64_t njobs) {
   REQUIRE_INIT();
-  PageExtractJob* d_jobs;
-  int* d_err;
-  HIP_TRY(pool_malloc((void**)&d_jobs,
-                      sizeof(PageExtractJob) * (njobs ? njobs : 1)));
-  HIP_TRY(pool_malloc((void**)&d_err, sizeof(int)));
-  HIP_TRY(hipMemset(d_err, 0, sizeof(int)));
-  HIP_TRY(hipMemcpy(d_jobs, h_jobs, sizeof(PageExtractJob) * njobs,
-                    hipMemcpyHostToDevice));
-  int blocks = (int)bg_imin64(njobs, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
-  hipLaunchKernelGGL(k_bss_batch, dim3(blocks), dim3(BG_BLOCK), 0, 0, d_jobs,
-                     njobs, d_err);
-  HIP_TRY(hipGetLastError());
   int err = 0;
-  HIP_TRY(hipMemcpy(&err, d_err, sizeof(int), hipMemcpyDeviceToHost));
-  (void)pool_release(d_jobs);
-  (void)pool_release(d_err);
+  if (int rc = run_job_batch<PageExtractJob>(
+          k_bss_batch, h_jobs, njobs,
+          grid_for(njobs, 1), &err))
+    return rc;
   if (err) return set_err(BG_ERR_INVALID, "bg_bss_batch: malformed page");
   return BG_OK;
 }
@@ -5645,22 +5596,11 @@ __global__ void k_page_extract_batch(const PageExtractJob* jobs, int64_t njobs,
 
 extern "C" int bg_page_extract_batch(const void* h_jobs, int64_t njobs) {
   REQUIRE_INIT();
-  PageExtractJob* d_jobs;
-  int* d_err;
-  HIP_TRY(pool_malloc((void**)&d_jobs, sizeof(PageExtractJob) * (njobs ? njobs : 1)));
-  HIP_TRY(pool_malloc((void**)&d_err, sizeof(int)));
-  HIP_TRY(hipMemset(d_err, 0, sizeof(int)));
-  HIP_TRY(hipMemcpy(d_jobs, h_jobs, sizeof(PageExtractJob) * njobs,
-                    hipMemcpyHostToDevice));
-  int blocks = (int)bg_imin64(njobs, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
-  hipLaunchKernelGGL(k_page_extract_batch, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                     d_jobs, njobs, d_err);
-  HIP_TRY(hipGetLastError());
   int err = 0;
-  HIP_TRY(hipMemcpy(&err, d_err, sizeof(int), hipMemcpyDeviceToHost));
-  (void)pool_release(d_jobs);
-  (void)pool_release(d_err);
+  if (int rc = run_job_batch<PageExtractJob>(
+          k_page_extract_batch, h_jobs, njobs,
+          grid_for(njobs, 1), &err))
+    return rc;
   if (err)
     return set_err(BG_ERR_UNSUPPORTED,
                    "bg_page_extract_batch: nulls or malformed page");
@@ -5694,24 +5634,11 @@ __global__ void k_dict_indices_batch(const DictIndicesJob* jobs, int64_t njobs,
 
 extern "C" int bg_dict_indices_batch(const void* h_jobs, int64_t njobs) {
   REQUIRE_INIT();
-  DictIndicesJob* d_jobs;
-  int* d_err;
-  HIP_TRY(pool_malloc((void**)&d_jobs, sizeof(DictIndicesJob) * (njobs ? njobs : 1)));
-  HIP_TRY(pool_malloc((void**)&d_err, sizeof(int)));
-  HIP_TRY(hipMemset(d_err, 0, sizeof(int)));
-  HIP_TRY(hipMemcpy(d_jobs, h_jobs, sizeof(DictIndicesJob) * njobs,
-                    hipMemcpyHostToDevice));
-  const int waves_per_block = BG_BLOCK / BG_WAVE;
-  int blocks = (int)bg_imin64((njobs + waves_per_block - 1) / waves_per_block,
-                              BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
-  hipLaunchKernelGGL(k_dict_indices_batch, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                     d_jobs, njobs, d_err);
-  HIP_TRY(hipGetLastError());
   int err = 0;
-  HIP_TRY(hipMemcpy(&err, d_err, sizeof(int), hipMemcpyDeviceToHost));
-  (void)pool_release(d_jobs);
-  (void)pool_release(d_err);
+  if (int rc = run_job_batch<DictIndicesJob>(
+          k_dict_indices_batch, h_jobs, njobs,
+          grid_for(njobs, BG_BLOCK / BG_WAVE), &err))
+    return rc;
   if (err == 2)
     return set_err(BG_ERR_UNSUPPORTED, "bg_dict_indices_batch: nulls");
   if (err)
@@ -5733,8 +5660,7 @@ __global__ void k_sub_i32(const int32_t* src, int64_t n, int32_t sub,
 extern "C" int bg_sub_i32(const void* d_src, int64_t n, int32_t sub,
                           void* d_out) {
   REQUIRE_INIT();
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(n);
   hipLaunchKernelGGL(k_sub_i32, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      (const int32_t*)d_src, n, sub, (int32_t*)d_out);
   HIP_TRY(hipGetLastError());
@@ -5790,14 +5716,13 @@ extern "C" int bg_gather_varlen(const void* d_src_data,
                                 void* d_out_data, int64_t out_data_cap,
                                 int64_t* out_total_bytes) {
   REQUIRE_INIT();
-  u64* d_lens;
-  i64* d_offs;
-  i64* d_total;
-  HIP_TRY(pool_malloc((void**)&d_lens, sizeof(u64) * (m ? m : 1)));
-  HIP_TRY(pool_malloc((void**)&d_offs, sizeof(i64) * (m ? m : 1)));
-  HIP_TRY(pool_malloc((void**)&d_total, sizeof(i64)));
-  int blocks = (int)bg_imin64((m + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  DevBuf<u64> d_lens;
+  DevBuf<i64> d_offs;
+  DevBuf<i64> d_total;
+  HIP_TRY(d_lens.alloc(m));
+  HIP_TRY(d_offs.alloc(m));
+  HIP_TRY(d_total.alloc(1));
+  int blocks = grid_for(m);
   hipLaunchKernelGGL(k_varlen_lens, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      d_src_offsets, d_idx, m, d_lens);
   int rc = scan_exclusive_i64(d_lens, m, d_offs, d_total);
@@ -5805,9 +5730,6 @@ extern "C" int bg_gather_varlen(const void* d_src_data,
   i64 total = 0;
   HIP_TRY(hipMemcpy(&total, d_total, sizeof(i64), hipMemcpyDeviceToHost));
   if (d_out_data == nullptr) {  // sizing call: report the needed bytes
-    (void)pool_release(d_lens);
-    (void)pool_release(d_offs);
-    (void)pool_release(d_total);
     *out_total_bytes = total;
     return BG_OK;
   }
@@ -5817,18 +5739,13 @@ extern "C" int bg_gather_varlen(const void* d_src_data,
     return set_err(BG_ERR_INVALID,
                    "bg_gather_varlen: >2GiB Utf8 data (LargeUtf8: later)");
   const int waves_per_block = BG_BLOCK / BG_WAVE;
-  int cblocks = (int)bg_imin64((m + waves_per_block - 1) / waves_per_block,
-                               BG_MAX_BLOCKS);
-  if (cblocks == 0) cblocks = 1;
+  int cblocks = grid_for(m, waves_per_block);
   hipLaunchKernelGGL(k_varlen_copy, dim3(cblocks), dim3(BG_BLOCK), 0, 0,
                      (const uint8_t*)d_src_data, d_src_offsets, d_idx, m,
                      d_offs, (uint8_t*)d_out_data, d_out_offsets);
   hipLaunchKernelGGL(k_varlen_tail, dim3(1), dim3(1), 0, 0, m, d_total,
                      d_out_offsets);
   HIP_TRY(hipGetLastError());
-  (void)pool_release(d_lens);
-  (void)pool_release(d_offs);
-  (void)pool_release(d_total);
   *out_total_bytes = total;
   return BG_OK;
 }
@@ -5861,9 +5778,7 @@ extern "C" int bg_gather_bits(const uint8_t* d_valid, const uint32_t* d_idx,
   REQUIRE_INIT();
   const int64_t nwords = (m + 63) / 64;
   const int waves_per_block = BG_BLOCK / BG_WAVE;
-  int blocks = (int)bg_imin64((nwords + waves_per_block - 1) / waves_per_block,
-                              BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(nwords, waves_per_block);
   hipLaunchKernelGGL(k_gather_bits, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      d_valid, d_idx, m, reinterpret_cast<u64*>(d_out_bits));
   HIP_TRY(hipGetLastError());
@@ -6007,25 +5922,21 @@ __global__ void k_lz4_compress_flat(const Lz4BlockJob* jobs, int64_t njobs,
 extern "C" int bg_lz4_compress_flat(const void* h_jobs, int64_t njobs,
                                     int64_t* h_block_sizes) {
   REQUIRE_INIT();
-  Lz4BlockJob* d_jobs;
-  int64_t* d_sizes;
-  HIP_TRY(pool_malloc((void**)&d_jobs, sizeof(Lz4BlockJob) * (njobs ? njobs : 1)));
-  HIP_TRY(pool_malloc((void**)&d_sizes, sizeof(int64_t) * (njobs ? njobs : 1)));
+  DevBuf<Lz4BlockJob> d_jobs;
+  DevBuf<int64_t> d_sizes;
+  HIP_TRY(d_jobs.alloc(njobs));
+  HIP_TRY(d_sizes.alloc(njobs));
   HIP_TRY(hipMemcpy(d_jobs, h_jobs, sizeof(Lz4BlockJob) * njobs,
                     hipMemcpyHostToDevice));
   const int waves_per_block = BG_BLOCK / BG_WAVE;
   const size_t lds = (size_t)waves_per_block * (1 << LZ4_HASH_LOG) *
                      sizeof(uint16_t);
-  int blocks = (int)bg_imin64((njobs + waves_per_block - 1) / waves_per_block,
-                              BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(njobs, waves_per_block);
   hipLaunchKernelGGL(k_lz4_compress_flat, dim3(blocks), dim3(BG_BLOCK), lds, 0,
                      d_jobs, njobs, d_sizes);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(h_block_sizes, d_sizes, sizeof(int64_t) * njobs,
                     hipMemcpyDeviceToHost));
-  (void)pool_release(d_jobs);
-  (void)pool_release(d_sizes);
   return BG_OK;
 }
 
@@ -6034,21 +5945,18 @@ extern "C" int bg_lz4_compress(const void* d_src, int64_t len,
                                int64_t* out_nblocks) {
   REQUIRE_INIT();
   const int64_t nblocks = (len + LZ4_BLOCK - 1) / LZ4_BLOCK;
-  int64_t* d_sizes;
-  HIP_TRY(pool_malloc((void**)&d_sizes, sizeof(int64_t) * (nblocks ? nblocks : 1)));
+  DevBuf<int64_t> d_sizes;
+  HIP_TRY(d_sizes.alloc(nblocks));
   const int waves_per_block = BG_BLOCK / BG_WAVE;
   const size_t lds = (size_t)waves_per_block * (1 << LZ4_HASH_LOG) *
                      sizeof(uint16_t);
-  int blocks = (int)bg_imin64((nblocks + waves_per_block - 1) / waves_per_block,
-                              BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(nblocks, waves_per_block);
   hipLaunchKernelGGL(k_lz4_compress, dim3(blocks), dim3(BG_BLOCK), lds, 0,
                      (const uint8_t*)d_src, len, (uint8_t*)d_out_slots,
                      (int64_t)LZ4_SLOT_STRIDE, d_sizes, nblocks);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(h_block_sizes, d_sizes, sizeof(int64_t) * nblocks,
                     hipMemcpyDeviceToHost));
-  (void)pool_release(d_sizes);
   *out_nblocks = nblocks;
   return BG_OK;
 }
@@ -6084,16 +5992,14 @@ __global__ void k_pack_blocks(const PackJob* jobs, int64_t njobs) {
 
 extern "C" int bg_pack_blocks(const void* h_jobs, int64_t njobs) {
   REQUIRE_INIT();
-  PackJob* d_jobs;
-  HIP_TRY(pool_malloc((void**)&d_jobs, sizeof(PackJob) * (njobs ? njobs : 1)));
+  DevBuf<PackJob> d_jobs;
+  HIP_TRY(d_jobs.alloc(njobs));
   HIP_TRY(hipMemcpy(d_jobs, h_jobs, sizeof(PackJob) * njobs,
                     hipMemcpyHostToDevice));
-  int blocks = (int)bg_imin64(njobs, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(njobs, 1);
   hipLaunchKernelGGL(k_pack_blocks, dim3(blocks), dim3(BG_BLOCK), 0, 0, d_jobs,
                      njobs);
   HIP_TRY(hipGetLastError());
-  (void)pool_release(d_jobs);
   return BG_OK;
 }
 
@@ -6348,22 +6254,21 @@ extern "C" int bg_hash_repartition_fused(const bg_column* key_cols,
   // hist + scan prework (same stability contract as the split)
   const int64_t nchunks = (n + PS_ROWS_PER_WAVE - 1) / PS_ROWS_PER_WAVE;
   const int64_t hist_len = (int64_t)k * (nchunks ? nchunks : 1);
-  uint32_t* d_pids;
-  u64* d_hist;
-  i64* d_start;
-  HIP_TRY(pool_malloc((void**)&d_pids, sizeof(uint32_t) * (n ? n : 1)));
-  HIP_TRY(pool_malloc((void**)&d_hist, sizeof(u64) * hist_len));
-  HIP_TRY(pool_malloc((void**)&d_start, sizeof(i64) * hist_len));
-  uint64_t* d_hashes;
-  HIP_TRY(pool_malloc((void**)&d_hashes, sizeof(u64) * (n ? n : 1)));
+  DevBuf<uint32_t> d_pids;
+  DevBuf<u64> d_hist;
+  DevBuf<i64> d_start;
+  HIP_TRY(d_pids.alloc(n));
+  HIP_TRY(d_hist.alloc(hist_len));
+  HIP_TRY(d_start.alloc(hist_len));
+  DevBuf<uint64_t> d_hashes;
+  HIP_TRY(d_hashes.alloc(n));
   int rc = bg_hash_columns(key_cols, nkeys, n, d_hashes);
   if (rc == BG_OK) rc = bg_partition_ids(d_hashes, n, k, d_pids);
-  (void)pool_release(d_hashes);
+  d_hashes.reset();  // n-sized: back to the pool before the scan allocates
   if (rc == BG_OK) {
     const int waves_per_block = BG_BLOCK / BG_WAVE;
     const size_t lds_hist = (size_t)waves_per_block * k * sizeof(uint32_t);
-    int blocks = (int)bg_imin64(nchunks, BG_MAX_BLOCKS);
-    if (blocks == 0) blocks = 1;
+    int blocks = grid_for(nchunks, 1);
     hipLaunchKernelGGL(k_part_hist, dim3(blocks), dim3(BG_BLOCK), lds_hist, 0,
                        d_pids, n, k, d_hist, nchunks);
     rc = scan_exclusive_i64(d_hist, hist_len, d_start, nullptr);
@@ -6372,27 +6277,20 @@ extern "C" int bg_hash_repartition_fused(const bg_column* key_cols,
     hipLaunchKernelGGL(k_extract_offsets, dim3(1), dim3(BG_BLOCK), 0, 0,
                        d_start, nchunks, k, n, d_offsets);
     const int64_t fm_threads = FM_WAVES * BG_WAVE;
-    int blocks = (int)bg_imin64(nchunks, BG_MAX_BLOCKS);
-    if (blocks == 0) blocks = 1;
-    hipEvent_t ev0, ev1;
-    (void)hipEventCreate(&ev0);
-    (void)hipEventCreate(&ev1);
-    (void)hipEventRecord(ev0, 0);
+    int blocks = grid_for(nchunks, 1);
+    EventPair ev;
+    (void)ev.create();
+    (void)hipEventRecord(ev.ev0, 0);
     hipLaunchKernelGGL(k_fused_materialize, dim3(blocks), dim3(fm_threads),
                        lds, 0, a, n, k, d_start, nchunks, d_indices, d_rank);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) rc = set_hip_err(e, "fused materialize");
-    (void)hipEventRecord(ev1, 0);
-    (void)hipEventSynchronize(ev1);
+    (void)hipEventRecord(ev.ev1, 0);
+    (void)hipEventSynchronize(ev.ev1);
     float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, ev0, ev1);
+    (void)hipEventElapsedTime(&ms, ev.ev0, ev.ev1);
     g_last_kernel_ms = (double)ms;
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
   }
-  (void)pool_release(d_pids);
-  (void)pool_release(d_hist);
-  (void)pool_release(d_start);
   return rc;
 }
 
@@ -6548,23 +6446,19 @@ __global__ void k_lz4_decompress(const Lz4Frame* frames, int64_t nframes,
 extern "C" int bg_lz4_decompress(const void* h_frames, int64_t nframes,
                                  int64_t* h_out_lens) {
   REQUIRE_INIT();
-  Lz4Frame* d_frames;
-  int64_t* d_lens;
-  HIP_TRY(pool_malloc((void**)&d_frames, sizeof(Lz4Frame) * (nframes ? nframes : 1)));
-  HIP_TRY(pool_malloc((void**)&d_lens, sizeof(int64_t) * (nframes ? nframes : 1)));
+  DevBuf<Lz4Frame> d_frames;
+  DevBuf<int64_t> d_lens;
+  HIP_TRY(d_frames.alloc(nframes));
+  HIP_TRY(d_lens.alloc(nframes));
   HIP_TRY(hipMemcpy(d_frames, h_frames, sizeof(Lz4Frame) * nframes,
                     hipMemcpyHostToDevice));
   const int waves_per_block = BG_BLOCK / BG_WAVE;
-  int blocks = (int)bg_imin64((nframes + waves_per_block - 1) / waves_per_block,
-                              BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(nframes, waves_per_block);
   hipLaunchKernelGGL(k_lz4_decompress, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      d_frames, nframes, d_lens);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(h_out_lens, d_lens, sizeof(int64_t) * nframes,
                     hipMemcpyDeviceToHost));
-  (void)pool_release(d_frames);
-  (void)pool_release(d_lens);
   return BG_OK;
 }
 
@@ -6615,8 +6509,7 @@ extern "C" int bg_bitcopy(const uint8_t* d_src_bits, int64_t nbits,
   REQUIRE_INIT();
   if (nbits <= 0) return BG_OK;
   int64_t words = ((dst_bit_off + nbits) >> 5) - (dst_bit_off >> 5) + 1;
-  int blocks = (int)bg_imin64((words + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(words);
   hipLaunchKernelGGL(k_bitcopy, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      d_src_bits, nbits, (uint32_t*)d_dst_bits, dst_bit_off);
   HIP_TRY(hipGetLastError());
@@ -7021,14 +6914,18 @@ extern "C" int bg_hashjoin_build2(const bg_column* keys, int32_t nkeys,
   t.n_build = n;
   const u64 nb = next_pow2_u64((u64)(n > 4 ? n * 2 : 8));
   t.mask = nb - 1;
-  HIP_TRY(pool_malloc((void**)&t.nodes, sizeof(ulong2) * (n ? n : 1)));
-  HIP_TRY(pool_malloc((void**)&t.head, sizeof(int) * nb));
-  HIP_TRY(hipMemset(t.head, 0xff, sizeof(int) * nb));
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  DevBuf<ulong2> nodes;
+  DevBuf<int> head;
+  HIP_TRY(nodes.alloc(n));
+  HIP_TRY(head.alloc((int64_t)nb));
+  HIP_TRY(hipMemset(head, 0xff, sizeof(int) * nb));
+  int blocks = grid_for(n);
   hipLaunchKernelGGL(k_join_build2, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                     t.bkeys, n, t.head, t.nodes, t.mask);
+                     t.bkeys, n, head.get(), nodes.get(), t.mask);
   HIP_TRY(hipGetLastError());
+  // the handle owns the table from here; bg_hashjoin_free2 releases it
+  t.nodes = nodes.detach();
+  t.head = head.detach();
   *out_handle = new BgJoinTable2(t);
   return BG_OK;
 }
@@ -7049,14 +6946,13 @@ extern "C" int bg_hashjoin_probe_count2(void* handle, const bg_column* keys,
     (void)pool_release(t->probe_offsets);
     t->probe_offsets = nullptr;
   }
-  uint32_t* d_counts;
-  i64* d_offs;
-  i64* d_total;
-  HIP_TRY(pool_malloc((void**)&d_counts, sizeof(uint32_t) * (n ? n : 1)));
-  HIP_TRY(pool_malloc((void**)&d_offs, sizeof(i64) * (n ? n : 1)));
-  HIP_TRY(pool_malloc((void**)&d_total, sizeof(i64)));
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  DevBuf<uint32_t> d_counts;
+  DevBuf<i64> d_offs;
+  DevBuf<i64> d_total;
+  HIP_TRY(d_counts.alloc(n));
+  HIP_TRY(d_offs.alloc(n));
+  HIP_TRY(d_total.alloc(1));
+  int blocks = grid_for(n);
   hipLaunchKernelGGL(k_join_count2, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      t->bkeys, pk, n, t->head, t->nodes, t->mask, join_type,
                      d_counts);
@@ -7065,9 +6961,7 @@ extern "C" int bg_hashjoin_probe_count2(void* handle, const bg_column* keys,
   if (rc != BG_OK) return rc;
   i64 total = 0;
   HIP_TRY(hipMemcpy(&total, d_total, sizeof(i64), hipMemcpyDeviceToHost));
-  (void)pool_release(d_counts);
-  (void)pool_release(d_total);
-  t->probe_offsets = d_offs;
+  t->probe_offsets = d_offs.detach();  // the handle owns it until free2
   t->probe_n = n;
   t->probe_jt = join_type;
   *out_matches = total;
@@ -7087,8 +6981,7 @@ extern "C" int bg_hashjoin_probe_fill2(void* handle, const bg_column* keys,
   if (!t->probe_offsets || t->probe_n != n || t->probe_jt != join_type)
     return set_err(BG_ERR_INVALID,
                    "call bg_hashjoin_probe_count2 first (same join_type)");
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(n);
   hipLaunchKernelGGL(k_join_fill2, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      t->bkeys, pk, n, t->head, t->nodes, t->mask, join_type,
                      t->probe_offsets, d_out_probe, d_out_build);
@@ -7260,9 +7153,7 @@ extern "C" int bg_eval_like(const bg_column* col, const char* const* terms,
     memcpy(a.terms[t], terms[t], (size_t)term_lens[t]);
   }
   const int64_t nwords = (n + 63) / 64;
-  int blocks = (int)bg_imin64((nwords * BG_WAVE + BG_BLOCK - 1) / BG_BLOCK,
-                              BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(nwords * BG_WAVE);
   hipLaunchKernelGGL(k_eval_like, dim3(blocks), dim3(BG_BLOCK), 0, 0, a, n,
                      (u64*)d_mask);
   HIP_TRY(hipGetLastError());
@@ -7368,19 +7259,16 @@ extern "C" int bg_eval_in(const bg_column* col, const int64_t* values,
   if (col->dtype != BG_DT_INT64 && col->dtype != BG_DT_INT32 &&
       col->dtype != BG_DT_DATE32 && col->dtype != BG_DT_DICT8)
     return set_err(BG_ERR_UNSUPPORTED, "bg_eval_in: integer/dict column");
-  int64_t* d_vals;
-  HIP_TRY(pool_malloc((void**)&d_vals, sizeof(int64_t) * 16));
+  DevBuf<int64_t> d_vals;
+  HIP_TRY(d_vals.alloc(16));
   HIP_TRY(hipMemcpy(d_vals, values, sizeof(int64_t) * nvalues,
                     hipMemcpyHostToDevice));
   const int64_t nwords = (n + 63) / 64;
-  int blocks = (int)bg_imin64((nwords * BG_WAVE + BG_BLOCK - 1) / BG_BLOCK,
-                              BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(nwords * BG_WAVE);
   hipLaunchKernelGGL(k_eval_in, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      (const uint8_t*)col->d_data, col->d_validity,
                      col->dtype, d_vals, nvalues, n, (u64*)d_mask);
   HIP_TRY(hipGetLastError());
-  (void)pool_release(d_vals);
   return BG_OK;
 }
 
@@ -7557,15 +7445,13 @@ extern "C" int bg_project_dec128_multi(
       return set_err(BG_ERR_UNSUPPORTED,
                      "bg_project_dec128_multi: dec128/int64 inputs");
   }
-  BgExprProg* d_p;
-  HIP_TRY(pool_malloc((void**)&d_p, sizeof(BgExprProg)));
+  DevBuf<BgExprProg> d_p;
+  HIP_TRY(d_p.alloc(1));
   HIP_TRY(hipMemcpy(d_p, &p, sizeof(BgExprProg), hipMemcpyHostToDevice));
-  int blocks = (int)bg_imin64((n + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
-  if (blocks == 0) blocks = 1;
+  int blocks = grid_for(n);
   hipLaunchKernelGGL(k_project_multi, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      d_p, n);
   int rc = hipGetLastError() == hipSuccess ? BG_OK : BG_ERR_HIP;
-  (void)pool_release(d_p);
   if (rc != BG_OK) return set_err(BG_ERR_HIP, "k_project_multi launch");
   return BG_OK;
 }

@@ -176,6 +176,14 @@ class GpuStageContext:
     def synchronize(self):
         _check(self.L.bg_synchronize(), "bg_synchronize")
 
+    def pool_stats(self):
+        """(live_bytes, live_buffers, cached_bytes) of the allocator pool."""
+        out = (ctypes.c_int64 * 3)()
+        _check(self.L.bg_pool_stats(
+            ctypes.byref(out, 0), ctypes.byref(out, 8),
+            ctypes.byref(out, 16)), "bg_pool_stats")
+        return tuple(out)
+
     # ---- columns ----
     def column(self, dtype: int, buf: DeviceBuffer, n: int,
                validity: DeviceBuffer = None, precision=0, scale=0,

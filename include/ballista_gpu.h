@@ -85,6 +85,11 @@ int bg_memcpy_d2h(void* h_dst, const void* d_src, uint64_t bytes);
 int bg_memcpy_dtod(void* d_dst, const void* d_src, uint64_t bytes);
 /* release the allocator pool's cached device memory back to HIP */
 int bg_pool_trim(void);
+/* allocator pool accounting (any out pointer may be NULL): live = buffers
+ * handed out (bg_malloc included) and not yet released, cached = bytes
+ * parked in the pool's free lists, which bg_pool_trim gives back */
+int bg_pool_stats(int64_t* live_bytes, int64_t* live_buffers,
+                  int64_t* cached_bytes);
 
 /* ---- columns ---- */
 typedef enum {
