@@ -37,6 +37,7 @@
 
 #include "../../include/ballista_gpu.h"
 #include "bg_ahash.h"
+#include "bg_internal.h"
 
 #define BG_BLOCK 256
 #define BG_MAX_BLOCKS 2048
@@ -268,7 +269,7 @@ static inline int grid_for(int64_t items, int64_t per_block = BG_BLOCK) {
 // flag) on `blocks` blocks and read the flag back into *err_out.  The
 // caller keeps its own grid rule and its own flag -> error mapping.
 template <typename Job, typename Kernel, typename... Extra>
-static int run_job_batch(Kernel kernel, const void* h_jobs, int64_t njobs,
+static int run_job_batch(Kernel kernel, const Job* h_jobs, int64_t njobs,
                          int blocks, int* err_out, Extra... extra) {
   DevBuf<Job> d_jobs;
   DevBuf<int> d_err;
@@ -1801,24 +1802,17 @@ extern "C" int bg_hashjoin_free(void* handle) {
 // groups with the existing mask->indices + gather machinery.
 // ---------------------------------------------------------------------------
 #define BG_MAX_AGGS 8
-#define BG_AGG_SUM_DEC128 0
-#define BG_AGG_SUM_I64 1
 // MIN/MAX store an order-preserving u64 encoding with atomicMax so the
 // zero-initialised slot is the identity (no per-slot init race):
 //   MAX_I64: enc = v ^ (1<<63);          decode: enc ^ (1<<63)
 //   MIN_I64: enc = ~(v ^ (1<<63));       decode: ~enc ^ (1<<63)
 // (groups always hold >= 1 row, so enc 0 is never read back as a value)
-#define BG_AGG_MIN_I64 2
-#define BG_AGG_MAX_I64 3
 // SUM over Float64: accumulation order is unordered (atomics), so low bits
 // are nondeterministic — covered by the reference comparator's 1e-6
 // relative float tolerance (benchmarks/src/lib.rs:35).
-#define BG_AGG_SUM_F64 4
 // MIN/MAX over Float64: totally-ordered u64 transform (negative values
 // bit-inverted, positives sign-flipped — IEEE total order incl. infs),
 // MIN stores the complement so atomicMax + zero identity works for both.
-#define BG_AGG_MIN_F64 5
-#define BG_AGG_MAX_F64 6
 
 struct AggArgs {
   int naggs;
@@ -1964,37 +1958,37 @@ __global__ void k_hashagg(KeyArgs keys, AggArgs aggs, const u64* mask_words,
       if (!bit_valid(aggs.a[a].valid, i)) continue;
       if (aggs.vmode) atomicAdd(&base[2], 1ull);
       switch (aggs.a[a].op) {
-        case BG_AGG_SUM_DEC128: {
+        case BG_AGG_OP_SUM_DEC128: {
           const ulong2 v =
               reinterpret_cast<const ulong2*>(aggs.a[a].data)[i];
           atomic_add_i128(base, base + 1, make_i128(v.x, (i64)v.y));
           break;
         }
-        case BG_AGG_SUM_I64: {
+        case BG_AGG_OP_SUM_I64: {
           const i64 v = reinterpret_cast<const int64_t*>(aggs.a[a].data)[i];
           // exact i64 sum in two's complement (wrap == i64 semantics);
           // keep the i128 carry so large sums stay exact at scale
           atomic_add_i128(base, base + 1, (i128)v);
           break;
         }
-        case BG_AGG_MAX_I64: {
+        case BG_AGG_OP_MAX_I64: {
           const u64 v = (u64) reinterpret_cast<const int64_t*>(
                             aggs.a[a].data)[i] ^ 0x8000000000000000ull;
           atomicMax(base, v);
           break;
         }
-        case BG_AGG_MIN_I64: {
+        case BG_AGG_OP_MIN_I64: {
           const u64 v = ~((u64) reinterpret_cast<const int64_t*>(
                               aggs.a[a].data)[i] ^ 0x8000000000000000ull);
           atomicMax(base, v);
           break;
         }
-        case BG_AGG_SUM_F64: {
+        case BG_AGG_OP_SUM_F64: {
           const double v = reinterpret_cast<const double*>(aggs.a[a].data)[i];
           atomicAdd(reinterpret_cast<double*>(base), v);
           break;
         }
-        case BG_AGG_MAX_F64: {
+        case BG_AGG_OP_MAX_F64: {
           // IEEE-754 totally-ordered u64 transform (sign-magnitude flip):
           // monotone for all finite values and infs, as the reference's
           // min_max.rs float compare is
@@ -2006,7 +2000,7 @@ __global__ void k_hashagg(KeyArgs keys, AggArgs aggs, const u64* mask_words,
           atomicMax(base, v);
           break;
         }
-        case BG_AGG_MIN_F64: {
+        case BG_AGG_OP_MIN_F64: {
           const u64 bits = (u64) reinterpret_cast<const int64_t*>(
                                aggs.a[a].data)[i];
           const u64 v = (bits & 0x8000000000000000ull)
@@ -2080,35 +2074,35 @@ __global__ void k_hashagg_lds(KeyArgs keys, AggArgs aggs,
       if (!bit_valid(aggs.a[a].valid, i)) continue;
       if (aggs.vmode) atomicAdd((unsigned long long*)&base[2], 1ull);
       switch (aggs.a[a].op) {
-        case BG_AGG_SUM_DEC128: {
+        case BG_AGG_OP_SUM_DEC128: {
           const ulong2 v =
               reinterpret_cast<const ulong2*>(aggs.a[a].data)[i];
           atomic_add_i128(base, base + 1, make_i128(v.x, (i64)v.y));
           break;
         }
-        case BG_AGG_SUM_I64: {
+        case BG_AGG_OP_SUM_I64: {
           const i64 v = reinterpret_cast<const int64_t*>(aggs.a[a].data)[i];
           atomic_add_i128(base, base + 1, (i128)v);
           break;
         }
-        case BG_AGG_MAX_I64: {
+        case BG_AGG_OP_MAX_I64: {
           const u64 v = (u64) reinterpret_cast<const int64_t*>(
                             aggs.a[a].data)[i] ^ 0x8000000000000000ull;
           atomicMax((unsigned long long*)base, v);
           break;
         }
-        case BG_AGG_MIN_I64: {
+        case BG_AGG_OP_MIN_I64: {
           const u64 v = ~((u64) reinterpret_cast<const int64_t*>(
                               aggs.a[a].data)[i] ^ 0x8000000000000000ull);
           atomicMax((unsigned long long*)base, v);
           break;
         }
-        case BG_AGG_SUM_F64: {
+        case BG_AGG_OP_SUM_F64: {
           const double v = reinterpret_cast<const double*>(aggs.a[a].data)[i];
           atomicAdd(reinterpret_cast<double*>(base), v);
           break;
         }
-        case BG_AGG_MAX_F64: {
+        case BG_AGG_OP_MAX_F64: {
           const u64 bits = (u64) reinterpret_cast<const int64_t*>(
                                aggs.a[a].data)[i];
           const u64 v = (bits & 0x8000000000000000ull)
@@ -2117,7 +2111,7 @@ __global__ void k_hashagg_lds(KeyArgs keys, AggArgs aggs,
           atomicMax((unsigned long long*)base, v);
           break;
         }
-        case BG_AGG_MIN_F64: {
+        case BG_AGG_OP_MIN_F64: {
           const u64 bits = (u64) reinterpret_cast<const int64_t*>(
                                aggs.a[a].data)[i];
           const u64 v = (bits & 0x8000000000000000ull)
@@ -2168,17 +2162,17 @@ __global__ void k_hashagg_lds(KeyArgs keys, AggArgs aggs,
       const u64* l = lrec + 2 + wpa * a;
       if (aggs.vmode) atomicAdd(&g[2], l[2]);
       switch (aggs.a[a].op) {
-        case BG_AGG_SUM_DEC128:
-        case BG_AGG_SUM_I64:
+        case BG_AGG_OP_SUM_DEC128:
+        case BG_AGG_OP_SUM_I64:
           atomic_add_i128(g, g + 1, make_i128(l[0], (i64)l[1]));
           break;
-        case BG_AGG_MAX_I64:
-        case BG_AGG_MIN_I64:
-        case BG_AGG_MAX_F64:
-        case BG_AGG_MIN_F64:
+        case BG_AGG_OP_MAX_I64:
+        case BG_AGG_OP_MIN_I64:
+        case BG_AGG_OP_MAX_F64:
+        case BG_AGG_OP_MIN_F64:
           atomicMax(g, l[0]);
           break;
-        case BG_AGG_SUM_F64: {
+        case BG_AGG_OP_SUM_F64: {
           double v;
           memcpy(&v, &l[0], 8);
           atomicAdd(reinterpret_cast<double*>(g), v);
@@ -2983,13 +2977,6 @@ extern "C" int bg_merge_join(const int64_t* d_build_sorted, int64_t nb,
 // tagged elements: tag&3==0 literal (len up to 4-byte extension),
 // 1 copy-1B (len 4-11, 11-bit offset), 2 copy-2B, 3 copy-4B.
 // ---------------------------------------------------------------------------
-struct SnappyPage {
-  const uint8_t* src;
-  uint8_t* dst;
-  int64_t src_len;
-  int64_t dst_cap;
-};
-
 // readfirstlane broadcast (SALU) — ~10x cheaper than __shfl's ds_bpermute
 // for the uniform lane-0 -> wave broadcasts in byte-serial decode loops
 __device__ __forceinline__ int bcast32(int v) {
@@ -3005,15 +2992,15 @@ __device__ __forceinline__ int64_t bcast64(int64_t v) {
 // and broadcasts each element; all 64 lanes execute the copy.  Overlapping
 // LZ77 copies (offset < length) replicate a pattern, which parallelises as
 // dst[i] = window[i % offset].  One wave per page.
-__global__ void k_snappy_decompress(const SnappyPage* pages, int64_t npages,
+__global__ void k_snappy_decompress(const bg_snappy_page* pages, int64_t npages,
                                     int64_t* out_lens /* -1 on error */) {
   const int64_t wave_global =
       ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / BG_WAVE;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) / BG_WAVE;
   const int lane = lane_id();
   for (int64_t p = wave_global; p < npages; p += nwaves) {
-    const uint8_t* base_s = pages[p].src;
-    uint8_t* base_d = pages[p].dst;
+    const uint8_t* base_s = pages[p].d_src;
+    uint8_t* base_d = pages[p].d_dst;
     const int64_t src_len = pages[p].src_len;
     int64_t si = 0, di = 0;
     int64_t ulen = 0;
@@ -3151,7 +3138,7 @@ struct SnapDesc {
 // 64-B window on the worst FLBA-decimal pages cost ~24 shuffle steps
 // instead of 24 dependent memory round trips — the tag stream is the only
 // serial part of snappy and this walks it at register speed.
-__global__ void k_snap_parse(const SnappyPage* __restrict__ pages,
+__global__ void k_snap_parse(const bg_snappy_page* __restrict__ pages,
                              int64_t npages, SnapDesc* __restrict__ descs,
                              const int64_t* __restrict__ desc_base,
                              int64_t* __restrict__ counts,
@@ -3166,7 +3153,7 @@ __global__ void k_snap_parse(const SnappyPage* __restrict__ pages,
       ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / BG_WAVE;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) / BG_WAVE;
   for (int64_t p = wave_global; p < npages; p += nwaves) {
-    const uint8_t* __restrict__ s = pages[p].src;
+    const uint8_t* __restrict__ s = pages[p].d_src;
     const int64_t src_len = pages[p].src_len;
     SnapDesc* d = descs + desc_base[p];
     int64_t si = 0, di = 0, ulen = 0, nd = 0;
@@ -3304,14 +3291,14 @@ __global__ void k_snap_parse(const SnappyPage* __restrict__ pages,
 // bytes are adjacent in src and dst, so the scattered per-lane accesses
 // stay within a few cache lines — and long literals replay wave-parallel
 // from the ballot of survivors.
-__global__ void k_snap_literals(const SnappyPage* __restrict__ pages,
+__global__ void k_snap_literals(const bg_snappy_page* __restrict__ pages,
                                 int64_t page0,
                                 const SnapDesc* __restrict__ descs,
                                 const int64_t* __restrict__ desc_base,
                                 const int64_t* __restrict__ counts) {
   const int64_t p = page0 + blockIdx.y;
-  const uint8_t* src = pages[p].src;
-  uint8_t* dst = pages[p].dst;
+  const uint8_t* src = pages[p].d_src;
+  uint8_t* dst = pages[p].d_dst;
   const SnapDesc* d = descs + desc_base[p];
   const int64_t nd = counts[p];
   const int waves_per_block = blockDim.x / BG_WAVE;
@@ -3364,7 +3351,7 @@ __global__ void k_snap_literals(const SnappyPage* __restrict__ pages,
 // longest such prefix executes concurrently, one match per lane.  Only
 // genuinely chained matches (window into the current batch — tight RLE
 // runs) fall back to the one-element wave-parallel path.
-__global__ void k_snap_matches(const SnappyPage* __restrict__ pages,
+__global__ void k_snap_matches(const bg_snappy_page* __restrict__ pages,
                                int64_t npages,
                                const SnapDesc* __restrict__ descs,
                                const int64_t* __restrict__ desc_base,
@@ -3376,7 +3363,7 @@ __global__ void k_snap_matches(const SnappyPage* __restrict__ pages,
   const int lane = lane_id();
   for (int64_t p = wave_global; p < npages; p += nwaves) {
     if (skip && skip[p]) continue;  // big pages replay via list ranking
-    uint8_t* dst = pages[p].dst;
+    uint8_t* dst = pages[p].d_dst;
     const SnapDesc* d = descs + desc_base[p];
     const int64_t nd = counts[p];
     int64_t e = 0;
@@ -3505,7 +3492,7 @@ __device__ __forceinline__ bool snap_decode_at(
 }
 
 struct SnapBigPage {
-  int64_t page_idx;  // into the SnappyPage array
+  int64_t page_idx;  // into the bg_snappy_page array
   int64_t arr_base;  // per-byte array base (bytes)
   int64_t seg_base;  // per-seg array base
   int64_t nsegs;
@@ -3514,7 +3501,7 @@ struct SnapBigPage {
 };
 
 // phase A: speculative per-segment chase
-__global__ void k_snapbig_spec(const SnappyPage* __restrict__ pages,
+__global__ void k_snapbig_spec(const bg_snappy_page* __restrict__ pages,
                                const SnapBigPage* __restrict__ bigs,
                                const int32_t* __restrict__ seg_page,
                                int64_t total_segs,
@@ -3531,8 +3518,8 @@ __global__ void k_snapbig_spec(const SnappyPage* __restrict__ pages,
        gs < total_segs; gs += (int64_t)gridDim.x * blockDim.x) {
     const SnapBigPage& bp = bigs[seg_page[gs]];
     const int64_t k = gs - bp.seg_base;
-    const SnappyPage& pg = pages[bp.page_idx];
-    const uint8_t* s = pg.src;
+    const bg_snappy_page& pg = pages[bp.page_idx];
+    const uint8_t* s = pg.d_src;
     const int64_t src_len = pg.src_len;
     int64_t o = k * bp.seg_sz;
     if (k == 0) {
@@ -3606,7 +3593,7 @@ __global__ void k_snapbig_spec(const SnappyPage* __restrict__ pages,
 //   w_land >= 0: landed on the segment's spec chain at this offset
 //   w_land == -1: walked past the segment end (exit = w_exit)
 //   w_land == -4: decode failed on the walk (malformed if entry is true)
-__global__ void k_snapbig_walk(const SnappyPage* __restrict__ pages,
+__global__ void k_snapbig_walk(const bg_snappy_page* __restrict__ pages,
                                const SnapBigPage* __restrict__ bigs,
                                const int32_t* __restrict__ seg_page,
                                int64_t total_segs,
@@ -3621,8 +3608,8 @@ __global__ void k_snapbig_walk(const SnappyPage* __restrict__ pages,
        gs < total_segs; gs += (int64_t)gridDim.x * blockDim.x) {
     const SnapBigPage& bp = bigs[seg_page[gs]];
     const int64_t k = gs - bp.seg_base;
-    const SnappyPage& pg = pages[bp.page_idx];
-    const uint8_t* s = pg.src;
+    const bg_snappy_page& pg = pages[bp.page_idx];
+    const uint8_t* s = pg.d_src;
     const int64_t src_len = pg.src_len;
     const int64_t e = k == 0 ? page_hdr[seg_page[gs]] : seg_exit[gs - 1];
     w_cnt[gs] = 0;
@@ -3664,7 +3651,7 @@ __global__ void k_snapbig_walk(const SnappyPage* __restrict__ pages,
 
 // phase B: one thread per page composes segment entries/prefixes from the
 // parallel walks (serial catch-up only on candidate mismatch)
-__global__ void k_snapbig_resolve(const SnappyPage* __restrict__ pages,
+__global__ void k_snapbig_resolve(const bg_snappy_page* __restrict__ pages,
                                   const SnapBigPage* __restrict__ bigs,
                                   int64_t nbig, unsigned long long* dbg_ctr,
                                   const uint16_t* __restrict__ next16,
@@ -3687,8 +3674,8 @@ __global__ void k_snapbig_resolve(const SnappyPage* __restrict__ pages,
   for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < nbig;
        b += (int64_t)gridDim.x * blockDim.x) {
     const SnapBigPage& bp = bigs[b];
-    const SnappyPage& pg = pages[bp.page_idx];
-    const uint8_t* s = pg.src;
+    const bg_snappy_page& pg = pages[bp.page_idx];
+    const uint8_t* s = pg.d_src;
     const int64_t src_len = pg.src_len;
     const int64_t hdr = page_hdr[b];
     const int64_t ulen = page_ulen[b];
@@ -3756,7 +3743,7 @@ __global__ void k_snapbig_resolve(const SnappyPage* __restrict__ pages,
 
 // phase C: one thread per live segment re-decodes its true chain and
 // emits descriptors at the precomputed positions (validation included)
-__global__ void k_snapbig_emit(const SnappyPage* __restrict__ pages,
+__global__ void k_snapbig_emit(const bg_snappy_page* __restrict__ pages,
                                const SnapBigPage* __restrict__ bigs,
                                const int32_t* __restrict__ seg_page,
                                int64_t total_segs,
@@ -3772,8 +3759,8 @@ __global__ void k_snapbig_emit(const SnappyPage* __restrict__ pages,
     if (seg_entry[gs] < 0) continue;
     const SnapBigPage& bp = bigs[seg_page[gs]];
     const int64_t k = gs - bp.seg_base;
-    const SnappyPage& pg = pages[bp.page_idx];
-    const uint8_t* s = pg.src;
+    const bg_snappy_page& pg = pages[bp.page_idx];
+    const uint8_t* s = pg.d_src;
     const int64_t src_len = pg.src_len;
     const int64_t ulen = page_ulen[seg_page[gs]];
     const int64_t seg_end =
@@ -3902,7 +3889,7 @@ __global__ void k_snap_par_double(const SnapBigPage* __restrict__ bigs,
   if (any) *changed = 1;
 }
 
-__global__ void k_snap_par_fill(const SnappyPage* __restrict__ pages,
+__global__ void k_snap_par_fill(const bg_snappy_page* __restrict__ pages,
                                 const SnapBigPage* __restrict__ bigs,
                                 int64_t nbig,
                                 const int64_t* __restrict__ lens,
@@ -3915,7 +3902,7 @@ __global__ void k_snap_par_fill(const SnappyPage* __restrict__ pages,
     const int64_t ulen = lens[bp.page_idx];
     if (ulen <= 0) continue;
     const uint32_t* p = P + bp.par_base;
-    uint8_t* out = pages[bp.page_idx].dst;
+    uint8_t* out = pages[bp.page_idx].d_dst;
     for (int64_t b = slot * blockDim.x + threadIdx.x; b < ulen;
          b += nslot * blockDim.x) {
       const uint32_t r = p[b];
@@ -3929,7 +3916,7 @@ __global__ void k_snap_par_fill(const SnappyPage* __restrict__ pages,
 
 // device arrays every phase of one call shares
 struct SnapDev {
-  DevBuf<SnappyPage> pages;
+  DevBuf<bg_snappy_page> pages;
   DevBuf<int64_t> lens, base, counts;
   DevBuf<SnapDesc> descs;
 };
@@ -3953,7 +3940,7 @@ static double snap_tick(bool dbg) {
              .count() / 1e6;
 }
 
-static bool snap_is_big(const SnappyPage& pg) {
+static bool snap_is_big(const bg_snappy_page& pg) {
   if (pg.src_len <= SNAPBIG_THRESHOLD) return false;
   if (pg.dst_cap > 0 && (double)pg.src_len > 0.85 * (double)pg.dst_cap)
     return false;
@@ -3962,7 +3949,7 @@ static bool snap_is_big(const SnappyPage& pg) {
 
 // Pure host step (no HIP call): which pages take the segmented parse and
 // which are replayed by list ranking.
-static SnapRoute snap_route(const SnappyPage* hp, int64_t npages) {
+static SnapRoute snap_route(const bg_snappy_page* hp, int64_t npages) {
   SnapRoute r;
   // giant pages (dict-fallback ~1 MB pages) go through the segmented
   // self-synchronizing parse; the wave chase handles the rest.  The
@@ -4046,7 +4033,7 @@ static SnapRoute snap_route(const SnappyPage* hp, int64_t npages) {
 // Wave-chase parse of every page the segmented parse does not take:
 // directly over the full page list when there is no big page, otherwise on
 // a compacted list whose counts/lens are scattered back to the full arrays.
-static int snap_parse_small(const SnapDev& d, const SnappyPage* hp,
+static int snap_parse_small(const SnapDev& d, const bg_snappy_page* hp,
                             const std::vector<int64_t>& base, int64_t npages,
                             bool any_big) {
   const int wpb1 = BG_BLOCK / BG_WAVE;  // parse waves per block
@@ -4059,7 +4046,7 @@ static int snap_parse_small(const SnapDev& d, const SnappyPage* hp,
     return BG_OK;
   }
   // small pages via the chase (on a compacted page list mapped back)
-  std::vector<SnappyPage> smalls;
+  std::vector<bg_snappy_page> smalls;
   std::vector<int64_t> small_map, small_base;
   for (int64_t p = 0; p < npages; ++p) {
     if (snap_is_big(hp[p])) continue;
@@ -4069,13 +4056,13 @@ static int snap_parse_small(const SnapDev& d, const SnappyPage* hp,
   }
   if (smalls.empty()) return BG_OK;
   const int64_t ns = (int64_t)smalls.size();
-  DevBuf<SnappyPage> d_small;
+  DevBuf<bg_snappy_page> d_small;
   DevBuf<int64_t> d_small_base, d_small_counts, d_small_lens;
   HIP_TRY(d_small.alloc(ns));
   HIP_TRY(d_small_base.alloc(ns));
   HIP_TRY(d_small_counts.alloc(ns));
   HIP_TRY(d_small_lens.alloc(ns));
-  HIP_TRY(hipMemcpy(d_small, smalls.data(), sizeof(SnappyPage) * ns,
+  HIP_TRY(hipMemcpy(d_small, smalls.data(), sizeof(bg_snappy_page) * ns,
                     hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_small_base, small_base.data(), sizeof(int64_t) * ns,
                     hipMemcpyHostToDevice));
@@ -4198,7 +4185,7 @@ static int snap_parse_segmented(const SnapDev& d, const SnapRoute& r,
 // List-ranking replay of par_pages (parents are built here, after the
 // literal roots have landed), in chunks of <= 4 GB of parent arrays:
 // init, scatter, up to 20 doubling rounds, fill.
-static int snap_replay_listrank(const SnapDev& d, const SnappyPage* hp,
+static int snap_replay_listrank(const SnapDev& d, const bg_snappy_page* hp,
                                 const std::vector<SnapBigPage>& par_pages,
                                 bool dbg, int* par_rounds) {
   DevBuf<int> d_changed;
@@ -4280,11 +4267,11 @@ static int snap_replay_listrank(const SnapDev& d, const SnappyPage* hp,
 /* Decompress npages independent Snappy blocks.  pages: HOST array copied
  * internally; each entry's src/dst are DEVICE pointers.  out_lens (host,
  * npages): decompressed length or -1 on malformed input. */
-extern "C" int bg_snappy_decompress(const void* h_pages, int64_t npages,
-                                    int64_t* h_out_lens) {
+extern "C" int bg_snappy_decompress(const bg_snappy_page* h_pages,
+                                    int64_t npages, int64_t* h_out_lens) {
   REQUIRE_INIT();
   if (npages <= 0) return BG_OK;
-  const SnappyPage* hp = (const SnappyPage*)h_pages;
+  const bg_snappy_page* hp = h_pages;
   std::vector<int64_t> base(npages + 1);
   base[0] = 0;
   for (int64_t p = 0; p < npages; ++p)
@@ -4295,7 +4282,7 @@ extern "C" int bg_snappy_decompress(const void* h_pages, int64_t npages,
   HIP_TRY(d.base.alloc(npages + 1));
   HIP_TRY(d.counts.alloc(npages));
   HIP_TRY(d.descs.alloc(base[npages]));
-  HIP_TRY(hipMemcpy(d.pages, h_pages, sizeof(SnappyPage) * npages,
+  HIP_TRY(hipMemcpy(d.pages, h_pages, sizeof(bg_snappy_page) * npages,
                     hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d.base, base.data(), sizeof(int64_t) * (npages + 1),
                     hipMemcpyHostToDevice));
@@ -4728,19 +4715,9 @@ extern "C" int bg_dict_indices(const void* d_page, int64_t page_len,
 //     stream (~0u for NULL slots),
 //   - n_present = how many values the page's value section holds.
 // ---------------------------------------------------------------------------
-struct DefLevelsJob {
-  const uint8_t* page;     // page start ([u32 dlen][levels]...)
-  uint32_t* vidx;          // u32[nvals] (page-local slice)
-  uint32_t* valid_out;     // column validity bitmap as u32 words
-  int64_t page_len;
-  int64_t nvals;
-  int64_t bit_off;         // absolute bit position of this page's slot 0
-  int64_t* n_present;
-};
-
-__device__ void k_def_levels_body(const DefLevelsJob& job, int* err) {
+__device__ void k_def_levels_body(const bg_def_levels_job& job, int* err) {
   if (lane_id() != 0) return;
-  const uint8_t* page = job.page;
+  const uint8_t* page = job.d_page;
   if (job.page_len < 4) { atomicExch(err, 3); return; }
   const uint32_t dlen = (uint32_t)page[0] | ((uint32_t)page[1] << 8) |
                         ((uint32_t)page[2] << 16) | ((uint32_t)page[3] << 24);
@@ -4755,15 +4732,15 @@ __device__ void k_def_levels_body(const DefLevelsJob& job, int* err) {
     const int64_t bit = job.bit_off + s;
     const int64_t w = bit >> 5;
     if (w != cur_w) {
-      if (cur_w >= 0 && cur) atomicOr(&job.valid_out[cur_w], cur);
+      if (cur_w >= 0 && cur) atomicOr(&job.d_valid_out[cur_w], cur);
       cur_w = w;
       cur = 0;
     }
     if (present) {
       cur |= 1u << (bit & 31);
-      job.vidx[s] = cnt++;
+      job.d_vidx[s] = cnt++;
     } else {
-      job.vidx[s] = 0xffffffffu;
+      job.d_vidx[s] = 0xffffffffu;
     }
     ++s;
   };
@@ -4791,12 +4768,12 @@ __device__ void k_def_levels_body(const DefLevelsJob& job, int* err) {
       for (int64_t t = 0; t < run && s < job.nvals; ++t) emit(v);
     }
   }
-  if (cur_w >= 0 && cur) atomicOr(&job.valid_out[cur_w], cur);
+  if (cur_w >= 0 && cur) atomicOr(&job.d_valid_out[cur_w], cur);
   if (s < job.nvals) { atomicExch(err, 3); return; }
-  *job.n_present = (int64_t)cnt;
+  *job.d_n_present = (int64_t)cnt;
 }
 
-__global__ void k_def_levels_batch(const DefLevelsJob* jobs, int64_t njobs,
+__global__ void k_def_levels_batch(const bg_def_levels_job* jobs, int64_t njobs,
                                    int* err) {
   const int64_t wave_global =
       ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / BG_WAVE;
@@ -4805,10 +4782,11 @@ __global__ void k_def_levels_batch(const DefLevelsJob* jobs, int64_t njobs,
     k_def_levels_body(jobs[j], err);
 }
 
-extern "C" int bg_def_levels_batch(const void* h_jobs, int64_t njobs) {
+extern "C" int bg_def_levels_batch(const bg_def_levels_job* h_jobs,
+                                   int64_t njobs) {
   REQUIRE_INIT();
   int err = 0;
-  if (int rc = run_job_batch<DefLevelsJob>(
+  if (int rc = run_job_batch(
           k_def_levels_batch, h_jobs, njobs,
           grid_for(njobs, BG_BLOCK / BG_WAVE), &err))
     return rc;
@@ -4833,24 +4811,6 @@ extern "C" int bg_def_levels_batch(const void* h_jobs, int64_t njobs) {
 // <= 8 (max_def <= 255); deeper nesting (max_rep > 1) is rejected by the
 // host reader.
 // ---------------------------------------------------------------------------
-struct ListLevelsJob {
-  const uint8_t* page;  // [u32 rlen][rep][u32 dlen][def][values]
-  int64_t page_len;
-  int64_t nslots;      // level entries (page header num_values)
-  int32_t max_def;
-  int32_t def_entry;   // min def meaning an element slot exists
-  int32_t def_valid;   // min def meaning the LIST itself is non-null
-                       // (1 for an optional list, 0 for a required one)
-  int32_t _pad;
-  int64_t row_base;    // pass 2: column-global bases
-  int64_t entry_base;
-  int64_t* counts;     // pass 1: [rows, entries, present, rlen]
-  int32_t* row_sizes;  // pass 2: entries per row (column-global index)
-  uint32_t* list_valid;  // pass 2: row-space bitmap words
-  uint32_t* elem_valid;  // pass 2: entry-space bitmap words
-  uint32_t* vidx;        // pass 2: PAGE-LOCAL slice (host offsets it)
-};
-
 struct LvlRd {
   const uint8_t* d;
   const uint8_t* end;
@@ -4923,10 +4883,10 @@ __device__ __forceinline__ int bg_bitwidth(int v) {
   return w < 1 ? 1 : w;
 }
 
-__device__ void k_list_levels_body(const ListLevelsJob& job, int pass,
+__device__ void k_list_levels_body(const bg_list_levels_job& job, int pass,
                                    int* err) {
   if (lane_id() != 0) return;
-  const uint8_t* page = job.page;
+  const uint8_t* page = job.d_page;
   const int64_t plen = job.page_len;
   if (plen < 8) { atomicExch(err, 4); return; }
   const uint32_t rlen = (uint32_t)page[0] | ((uint32_t)page[1] << 8) |
@@ -4963,11 +4923,11 @@ __device__ void k_list_levels_body(const ListLevelsJob& job, int pass,
       cur_row = job.row_base + rows;
       ++rows;
       if (pass == 2) {
-        job.row_sizes[cur_row] = 0;
+        job.d_row_sizes[cur_row] = 0;
         if (def >= job.def_valid) {
           const int64_t w = cur_row >> 5;
           if (w != lv_w) {
-            if (lv_w >= 0 && lv_cur) atomicOr(&job.list_valid[lv_w], lv_cur);
+            if (lv_w >= 0 && lv_cur) atomicOr(&job.d_list_valid[lv_w], lv_cur);
             lv_w = w;
             lv_cur = 0;
           }
@@ -4978,18 +4938,18 @@ __device__ void k_list_levels_body(const ListLevelsJob& job, int pass,
     if (def >= job.def_entry) {
       if (pass == 2) {
         const int64_t ent = job.entry_base + entries;
-        job.row_sizes[cur_row] += 1;
+        job.d_row_sizes[cur_row] += 1;
         if (def == job.max_def) {
           const int64_t w = ent >> 5;
           if (w != ev_w) {
-            if (ev_w >= 0 && ev_cur) atomicOr(&job.elem_valid[ev_w], ev_cur);
+            if (ev_w >= 0 && ev_cur) atomicOr(&job.d_elem_valid[ev_w], ev_cur);
             ev_w = w;
             ev_cur = 0;
           }
           ev_cur |= 1u << (ent & 31);
-          job.vidx[entries] = (uint32_t)present;
+          job.d_vidx[entries] = (uint32_t)present;
         } else {
-          job.vidx[entries] = 0xffffffffu;
+          job.d_vidx[entries] = 0xffffffffu;
         }
       }
       ++entries;
@@ -4997,18 +4957,18 @@ __device__ void k_list_levels_body(const ListLevelsJob& job, int pass,
     if (def == job.max_def) ++present;
   }
   if (pass == 2) {
-    if (lv_w >= 0 && lv_cur) atomicOr(&job.list_valid[lv_w], lv_cur);
-    if (ev_w >= 0 && ev_cur) atomicOr(&job.elem_valid[ev_w], ev_cur);
+    if (lv_w >= 0 && lv_cur) atomicOr(&job.d_list_valid[lv_w], lv_cur);
+    if (ev_w >= 0 && ev_cur) atomicOr(&job.d_elem_valid[ev_w], ev_cur);
   } else {
-    job.counts[0] = rows;
-    job.counts[1] = entries;
-    job.counts[2] = present;
-    job.counts[3] = (int64_t)rlen;
+    job.d_counts[0] = rows;
+    job.d_counts[1] = entries;
+    job.d_counts[2] = present;
+    job.d_counts[3] = (int64_t)rlen;
   }
 }
 
-__global__ void k_list_levels_batch(const ListLevelsJob* jobs, int64_t njobs,
-                                    int pass, int* err) {
+__global__ void k_list_levels_batch(const bg_list_levels_job* jobs,
+                                    int64_t njobs, int pass, int* err) {
   const int64_t wave_global =
       ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / BG_WAVE;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) / BG_WAVE;
@@ -5016,12 +4976,12 @@ __global__ void k_list_levels_batch(const ListLevelsJob* jobs, int64_t njobs,
     k_list_levels_body(jobs[j], pass, err);
 }
 
-extern "C" int bg_list_levels_batch(const void* h_jobs, int64_t njobs,
-                                    int32_t pass) {
+extern "C" int bg_list_levels_batch(const bg_list_levels_job* h_jobs,
+                                    int64_t njobs, int32_t pass) {
   REQUIRE_INIT();
   if (njobs <= 0) return BG_OK;
   int err = 0;
-  if (int rc = run_job_batch<ListLevelsJob>(
+  if (int rc = run_job_batch(
           k_list_levels_batch, h_jobs, njobs,
           grid_for(njobs, BG_BLOCK / BG_WAVE), &err, (int)pass))
     return rc;
@@ -5139,21 +5099,9 @@ struct DbpStream {
   }
 };
 
-struct DeltaBpJob {
-  const uint8_t* page;   // page start ([u32 dlen][levels] when has_def)
-  uint8_t* out;          // i32/i64 column slice (slot-addressed)
-  int64_t page_len;
-  int64_t nvals;         // slots in this page
-  int64_t esz;           // 4 or 8 (output element width)
-  int32_t has_def;       // 0 none, 2 nullable
-  int32_t _pad;
-  const uint32_t* vidx;
-  const int64_t* n_present;
-};
-
-__device__ void k_delta_bp_body(const DeltaBpJob& job, int* err) {
+__device__ void k_delta_bp_body(const bg_delta_bp_job& job, int* err) {
   if (lane_id() != 0) return;
-  const uint8_t* p = job.page;
+  const uint8_t* p = job.d_page;
   const uint8_t* pend = p + job.page_len;
   if (job.has_def) {
     if (job.page_len < 4) { atomicExch(err, 3); return; }
@@ -5164,7 +5112,7 @@ __device__ void k_delta_bp_body(const DeltaBpJob& job, int* err) {
   }
   DbpStream st;
   if (!st.init(p, pend)) { atomicExch(err, 3); return; }
-  const int64_t want = job.has_def == 2 ? *job.n_present : job.nvals;
+  const int64_t want = job.has_def == 2 ? *job.d_n_present : job.nvals;
   if ((int64_t)st.total < want || want == 0) {
     if (want != 0) atomicExch(err, 3);
     return;
@@ -5172,12 +5120,12 @@ __device__ void k_delta_bp_body(const DeltaBpJob& job, int* err) {
   int64_t slot = 0;
   auto emit = [&](i64 v) {
     if (job.has_def == 2)
-      while (slot < job.nvals && job.vidx[slot] == 0xffffffffu) ++slot;
+      while (slot < job.nvals && job.d_vidx[slot] == 0xffffffffu) ++slot;
     if (slot < job.nvals) {
       if (job.esz == 8)
-        *(int64_t*)(job.out + slot * 8) = v;
+        *(int64_t*)(job.d_out + slot * 8) = v;
       else
-        *(int32_t*)(job.out + slot * 4) = (int32_t)v;
+        *(int32_t*)(job.d_out + slot * 4) = (int32_t)v;
       ++slot;
     }
   };
@@ -5196,23 +5144,10 @@ __device__ void k_delta_bp_body(const DeltaBpJob& job, int* err) {
 // string from its predecessor's prefix + its suffix at the final
 // offsets (lane-0 serial per page; strings share prefixes only within
 // a page).
-struct DeltaBaJob {
-  const uint8_t* page;
-  int64_t* lens_out;     // slot lengths
-  int64_t* srcaddr_out;  // pass 1: byte addresses (enc 6) or 0 (enc 7)
-  const int32_t* offs32; // pass 2 (enc 7): final column offsets
-  uint8_t* data_out;     // pass 2 (enc 7): column data base
-  int64_t page_len;
-  int64_t nvals;
-  int32_t has_def;
-  int32_t enc;           // 6 or 7
-  const uint32_t* vidx;
-  const int64_t* n_present;
-};
-
-__device__ void k_delta_ba_body(const DeltaBaJob& job, int pass, int* err) {
+__device__ void k_delta_ba_body(const bg_delta_ba_job& job, int pass,
+                                int* err) {
   if (lane_id() != 0) return;
-  const uint8_t* p = job.page;
+  const uint8_t* p = job.d_page;
   const uint8_t* pend = p + job.page_len;
   if (job.has_def) {
     if (job.page_len < 4) { atomicExch(err, 3); return; }
@@ -5221,11 +5156,11 @@ __device__ void k_delta_ba_body(const DeltaBaJob& job, int pass, int* err) {
     p += 4 + dlen;
     if (p > pend) { atomicExch(err, 3); return; }
   }
-  const int64_t want = job.has_def == 2 ? *job.n_present : job.nvals;
+  const int64_t want = job.has_def == 2 ? *job.d_n_present : job.nvals;
   if (pass == 1)
     for (int64_t t = 0; t < job.nvals; ++t) {
-      job.lens_out[t] = 0;
-      job.srcaddr_out[t] = 0;
+      job.d_lens_out[t] = 0;
+      job.d_srcaddr_out[t] = 0;
     }
   if (want == 0) return;
   if (job.enc == 6) {
@@ -5242,10 +5177,10 @@ __device__ void k_delta_ba_body(const DeltaBaJob& job, int pass, int* err) {
     int64_t slot = 0, cursor = 0;
     auto emit = [&](i64 ln) {
       if (job.has_def == 2)
-        while (slot < job.nvals && job.vidx[slot] == 0xffffffffu) ++slot;
+        while (slot < job.nvals && job.d_vidx[slot] == 0xffffffffu) ++slot;
       if (slot < job.nvals) {
-        job.lens_out[slot] = ln;
-        job.srcaddr_out[slot] = (int64_t)(uintptr_t)(bytes + cursor);
+        job.d_lens_out[slot] = ln;
+        job.d_srcaddr_out[slot] = (int64_t)(uintptr_t)(bytes + cursor);
         ++slot;
       }
       cursor += ln;
@@ -5283,17 +5218,17 @@ __device__ void k_delta_ba_body(const DeltaBaJob& job, int pass, int* err) {
     if (first && plen != 0) return false;  // nothing to prefix from
     if (!first && plen > prev_len) return false;
     if (job.has_def == 2)
-      while (slot < job.nvals && job.vidx[slot] == 0xffffffffu) ++slot;
+      while (slot < job.nvals && job.d_vidx[slot] == 0xffffffffu) ++slot;
     if (slot < job.nvals) {
       if (pass == 1) {
-        job.lens_out[slot] = plen + slen;
+        job.d_lens_out[slot] = plen + slen;
         // srcaddr stays 0: k_ba_copy skips, pass 2 reconstructs
       } else {
-        const int64_t off = (int64_t)job.offs32[slot];
-        uint8_t* dst = job.data_out + off;
+        const int64_t off = (int64_t)job.d_offs32[slot];
+        uint8_t* dst = job.d_data_out + off;
         if (!first)
           for (int64_t b = 0; b < plen; ++b)
-            dst[b] = job.data_out[prev_off + b];
+            dst[b] = job.d_data_out[prev_off + b];
         for (int64_t b = 0; b < slen; ++b) dst[plen + b] = sbytes[cursor + b];
         prev_off = off;
       }
@@ -5312,7 +5247,7 @@ __device__ void k_delta_ba_body(const DeltaBaJob& job, int pass, int* err) {
   if (sbytes + cursor > pend) atomicExch(err, 3);
 }
 
-__global__ void k_delta_ba_batch(const DeltaBaJob* jobs, int64_t njobs,
+__global__ void k_delta_ba_batch(const bg_delta_ba_job* jobs, int64_t njobs,
                                  int pass, int* err) {
   const int64_t wave_global =
       ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / BG_WAVE;
@@ -5321,11 +5256,11 @@ __global__ void k_delta_ba_batch(const DeltaBaJob* jobs, int64_t njobs,
     k_delta_ba_body(jobs[j], pass, err);
 }
 
-extern "C" int bg_delta_ba_batch(const void* h_jobs, int64_t njobs,
+extern "C" int bg_delta_ba_batch(const bg_delta_ba_job* h_jobs, int64_t njobs,
                                  int32_t pass) {
   REQUIRE_INIT();
   int err = 0;
-  if (int rc = run_job_batch<DeltaBaJob>(
+  if (int rc = run_job_batch(
           k_delta_ba_batch, h_jobs, njobs,
           grid_for(njobs, BG_BLOCK / BG_WAVE), &err, (int)pass))
     return rc;
@@ -5334,7 +5269,7 @@ extern "C" int bg_delta_ba_batch(const void* h_jobs, int64_t njobs,
   return BG_OK;
 }
 
-__global__ void k_delta_bp_batch(const DeltaBpJob* jobs, int64_t njobs,
+__global__ void k_delta_bp_batch(const bg_delta_bp_job* jobs, int64_t njobs,
                                  int* err) {
   const int64_t wave_global =
       ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / BG_WAVE;
@@ -5343,10 +5278,10 @@ __global__ void k_delta_bp_batch(const DeltaBpJob* jobs, int64_t njobs,
     k_delta_bp_body(jobs[j], err);
 }
 
-extern "C" int bg_delta_bp_batch(const void* h_jobs, int64_t njobs) {
+extern "C" int bg_delta_bp_batch(const bg_delta_bp_job* h_jobs, int64_t njobs) {
   REQUIRE_INIT();
   int err = 0;
-  if (int rc = run_job_batch<DeltaBpJob>(
+  if (int rc = run_job_batch(
           k_delta_bp_batch, h_jobs, njobs,
           grid_for(njobs, BG_BLOCK / BG_WAVE), &err))
     return rc;
@@ -5364,27 +5299,15 @@ extern "C" int bg_delta_bp_batch(const void* h_jobs, int64_t njobs) {
 // one exclusive scan over the lengths + a parallel copy
 // (bg_ba_materialize) into Arrow offsets+data form.
 // ---------------------------------------------------------------------------
-struct BaPageJob {
-  const uint8_t* page;
-  int64_t* lens_out;     // i64[nvals] slice (slot lengths; NULL slot = 0)
-  int64_t* srcaddr_out;  // i64[nvals] slice (device address of the bytes)
-  int64_t page_len;
-  int64_t nvals;
-  int32_t has_def;       // 0 none, 2 nullable
-  int32_t _pad;
-  const uint32_t* vidx;
-  const int64_t* n_present;
-};
-
-__device__ void k_ba_extract_body(const BaPageJob& job, int* err) {
+__device__ void k_ba_extract_body(const bg_ba_page_job& job, int* err) {
   const int lane = lane_id();
   for (int64_t t = lane; t < job.nvals; t += BG_WAVE) {
-    job.lens_out[t] = 0;
-    job.srcaddr_out[t] = 0;
+    job.d_lens_out[t] = 0;
+    job.d_srcaddr_out[t] = 0;
   }
   __builtin_amdgcn_wave_barrier();
   if (lane != 0) return;
-  const uint8_t* p = job.page;
+  const uint8_t* p = job.d_page;
   int64_t pos = 0;
   if (job.has_def) {
     if (job.page_len < 4) { atomicExch(err, 3); return; }
@@ -5393,20 +5316,20 @@ __device__ void k_ba_extract_body(const BaPageJob& job, int* err) {
     pos = 4 + (int64_t)dlen;
   }
   for (int64_t s = 0; s < job.nvals; ++s) {
-    if (job.has_def == 2 && job.vidx[s] == 0xffffffffu) continue;
+    if (job.has_def == 2 && job.d_vidx[s] == 0xffffffffu) continue;
     if (pos + 4 > job.page_len) { atomicExch(err, 3); return; }
     const uint32_t len = (uint32_t)p[pos] | ((uint32_t)p[pos + 1] << 8) |
                          ((uint32_t)p[pos + 2] << 16) |
                          ((uint32_t)p[pos + 3] << 24);
     pos += 4;
     if (pos + (int64_t)len > job.page_len) { atomicExch(err, 3); return; }
-    job.lens_out[s] = (int64_t)len;
-    job.srcaddr_out[s] = (int64_t)(uintptr_t)(p + pos);
+    job.d_lens_out[s] = (int64_t)len;
+    job.d_srcaddr_out[s] = (int64_t)(uintptr_t)(p + pos);
     pos += (int64_t)len;
   }
 }
 
-__global__ void k_ba_extract_batch(const BaPageJob* jobs, int64_t njobs,
+__global__ void k_ba_extract_batch(const bg_ba_page_job* jobs, int64_t njobs,
                                    int* err) {
   const int64_t wave_global =
       ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / BG_WAVE;
@@ -5415,10 +5338,11 @@ __global__ void k_ba_extract_batch(const BaPageJob* jobs, int64_t njobs,
     k_ba_extract_body(jobs[j], err);
 }
 
-extern "C" int bg_ba_extract_batch(const void* h_jobs, int64_t njobs) {
+extern "C" int bg_ba_extract_batch(const bg_ba_page_job* h_jobs,
+                                   int64_t njobs) {
   REQUIRE_INIT();
   int err = 0;
-  if (int rc = run_job_batch<BaPageJob>(
+  if (int rc = run_job_batch(
           k_ba_extract_batch, h_jobs, njobs,
           grid_for(njobs, BG_BLOCK / BG_WAVE), &err))
     return rc;
@@ -5515,18 +5439,6 @@ extern "C" int bg_ba_materialize(const int64_t* d_lens,
 // page) starves the GPU when chunks hold few pages — these take the whole
 // column's page list in one call.
 // ---------------------------------------------------------------------------
-struct PageExtractJob {
-  const uint8_t* page;
-  uint8_t* out;
-  int64_t page_len;
-  int64_t nvals;
-  int64_t src_esz;
-  int32_t has_def;  // 0 none, 1 validate-all-present, 2 nullable (vidx)
-  int32_t flba_reverse;
-  const uint32_t* vidx;      // mode 2: per-slot value index, ~0u = null
-  const int64_t* n_present;  // mode 2: value count in this page
-};
-
 // ---------------------------------------------------------------------------
 // BYTE_STREAM_SPLIT (encoding 9, fixed-width values): the page stores the
 // k-th byte of every value contiguously (k streams of n_present bytes) —
@@ -5534,11 +5446,11 @@ struct PageExtractJob {
 // through vidx (spec Encodings.md; the reference's parquet crate
 // byte_stream_split decoder).
 // ---------------------------------------------------------------------------
-__global__ void k_bss_batch(const PageExtractJob* jobs, int64_t njobs,
+__global__ void k_bss_batch(const bg_page_extract_job* jobs, int64_t njobs,
                             int* err) {
   for (int64_t j = blockIdx.x; j < njobs; j += gridDim.x) {
-    const PageExtractJob job = jobs[j];
-    const uint8_t* page = job.page;
+    const bg_page_extract_job job = jobs[j];
+    const uint8_t* page = job.d_page;
     int64_t voff = 0;
     if (job.has_def) {
       if (job.page_len < 4) {
@@ -5551,7 +5463,7 @@ __global__ void k_bss_batch(const PageExtractJob* jobs, int64_t njobs,
       voff = 4 + (int64_t)dlen;
     }
     const int64_t npres =
-        job.has_def == 2 ? *job.n_present : job.nvals;
+        job.has_def == 2 ? *job.d_n_present : job.nvals;
     if (voff + npres * job.src_esz > job.page_len) {
       if (threadIdx.x == 0) atomicExch(err, 3);
       continue;
@@ -5560,23 +5472,23 @@ __global__ void k_bss_batch(const PageExtractJob* jobs, int64_t njobs,
     for (int64_t s2 = threadIdx.x; s2 < job.nvals; s2 += blockDim.x) {
       int64_t k;
       if (job.has_def == 2) {
-        const uint32_t ix = job.vidx[s2];
+        const uint32_t ix = job.d_vidx[s2];
         if (ix == 0xffffffffu) continue;
         k = (int64_t)ix;
       } else {
         k = s2;
       }
-      uint8_t* dst = job.out + s2 * job.src_esz;
+      uint8_t* dst = job.d_out + s2 * job.src_esz;
       for (int64_t b = 0; b < job.src_esz; ++b)
         dst[b] = v[b * npres + k];
     }
   }
 }
 
-extern "C" int bg_bss_batch(const void* h_jobs, int64_t njobs) {
+extern "C" int bg_bss_batch(const bg_page_extract_job* h_jobs, int64_t njobs) {
   REQUIRE_INIT();
   int err = 0;
-  if (int rc = run_job_batch<PageExtractJob>(
+  if (int rc = run_job_batch(
           k_bss_batch, h_jobs, njobs,
           grid_for(njobs, 1), &err))
     return rc;
@@ -5584,20 +5496,21 @@ extern "C" int bg_bss_batch(const void* h_jobs, int64_t njobs) {
   return BG_OK;
 }
 
-__global__ void k_page_extract_batch(const PageExtractJob* jobs, int64_t njobs,
-                                     int* err) {
+__global__ void k_page_extract_batch(const bg_page_extract_job* jobs,
+                                     int64_t njobs, int* err) {
   for (int64_t j = blockIdx.x; j < njobs; j += gridDim.x) {
-    const PageExtractJob job = jobs[j];
-    k_page_extract_body(job.page, job.page_len, job.out, job.nvals,
+    const bg_page_extract_job job = jobs[j];
+    k_page_extract_body(job.d_page, job.page_len, job.d_out, job.nvals,
                         job.src_esz, job.has_def, job.flba_reverse,
-                        job.vidx, job.n_present, err);
+                        job.d_vidx, job.d_n_present, err);
   }
 }
 
-extern "C" int bg_page_extract_batch(const void* h_jobs, int64_t njobs) {
+extern "C" int bg_page_extract_batch(const bg_page_extract_job* h_jobs,
+                                     int64_t njobs) {
   REQUIRE_INIT();
   int err = 0;
-  if (int rc = run_job_batch<PageExtractJob>(
+  if (int rc = run_job_batch(
           k_page_extract_batch, h_jobs, njobs,
           grid_for(njobs, 1), &err))
     return rc;
@@ -5607,35 +5520,24 @@ extern "C" int bg_page_extract_batch(const void* h_jobs, int64_t njobs) {
   return BG_OK;
 }
 
-struct DictIndicesJob {
-  const uint8_t* page;
-  uint32_t* out_idx;
-  int64_t page_len;
-  int64_t nvals;
-  int32_t has_def;  // 0 none, 1 validate-all-present, 2 nullable (vidx)
-  int32_t _pad;
-  const uint32_t* vidx;      // mode 2
-  const int64_t* n_present;  // mode 2
-  uint32_t* dense;           // mode 2: scratch for the packed index stream
-};
-
-__global__ void k_dict_indices_batch(const DictIndicesJob* jobs, int64_t njobs,
-                                     int* err) {
+__global__ void k_dict_indices_batch(const bg_dict_indices_job* jobs,
+                                     int64_t njobs, int* err) {
   const int64_t wave_global =
       ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / BG_WAVE;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) / BG_WAVE;
   for (int64_t j = wave_global; j < njobs; j += nwaves) {
-    const DictIndicesJob job = jobs[j];
-    k_dict_indices_body(job.page, job.page_len, job.nvals, job.has_def,
-                        job.out_idx, job.vidx, job.n_present, job.dense,
+    const bg_dict_indices_job job = jobs[j];
+    k_dict_indices_body(job.d_page, job.page_len, job.nvals, job.has_def,
+                        job.d_out_idx, job.d_vidx, job.d_n_present, job.d_dense,
                         err);
   }
 }
 
-extern "C" int bg_dict_indices_batch(const void* h_jobs, int64_t njobs) {
+extern "C" int bg_dict_indices_batch(const bg_dict_indices_job* h_jobs,
+                                     int64_t njobs) {
   REQUIRE_INIT();
   int err = 0;
-  if (int rc = run_job_batch<DictIndicesJob>(
+  if (int rc = run_job_batch(
           k_dict_indices_batch, h_jobs, njobs,
           grid_for(njobs, BG_BLOCK / BG_WAVE), &err))
     return rc;
@@ -5795,9 +5697,7 @@ extern "C" int bg_gather_bits(const uint8_t* d_valid, const uint32_t* d_idx,
 // Frame assembly (constant 7-byte header 04224d18/40/40/c0 + [u32 size]
 // blocks + end mark) is host-side glue over the returned sizes.
 // ---------------------------------------------------------------------------
-#define LZ4_BLOCK 65536
 #define LZ4_HASH_LOG 12
-#define LZ4_SLOT_STRIDE (LZ4_BLOCK + 8)
 
 // wave-cooperative single-block compress; returns csize or -blen (stored)
 __device__ int64_t lz4_compress_one(const uint8_t* s, int32_t blen,
@@ -5886,9 +5786,9 @@ __global__ void k_lz4_compress(const uint8_t* src, int64_t len,
       ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / BG_WAVE;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) / BG_WAVE;
   for (int64_t b = wave_global; b < nblocks; b += nwaves) {
-    const int64_t boff = b * LZ4_BLOCK;
-    const int32_t blen = (int32_t)(len - boff < LZ4_BLOCK ? len - boff
-                                                          : LZ4_BLOCK);
+    const int64_t boff = b * BG_LZ4_BLOCK;
+    const int32_t blen = (int32_t)(len - boff < BG_LZ4_BLOCK ? len - boff
+                                                          : BG_LZ4_BLOCK);
     const int64_t r = lz4_compress_one(src + boff, blen,
                                        out_slots + b * slot_stride, tab);
     if (lane_id() == 0) block_sizes[b] = r;
@@ -5896,14 +5796,7 @@ __global__ void k_lz4_compress(const uint8_t* src, int64_t len,
 }
 
 // flat batched form: one wave per (buffer, block) pair across many buffers
-struct Lz4BlockJob {
-  const uint8_t* src;
-  uint8_t* dst_slot;
-  int32_t blen;
-  int32_t _pad;
-};
-
-__global__ void k_lz4_compress_flat(const Lz4BlockJob* jobs, int64_t njobs,
+__global__ void k_lz4_compress_flat(const bg_lz4_block_job* jobs, int64_t njobs,
                                     int64_t* block_sizes) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   uint16_t* tab_all = reinterpret_cast<uint16_t*>(smem_raw);
@@ -5913,20 +5806,21 @@ __global__ void k_lz4_compress_flat(const Lz4BlockJob* jobs, int64_t njobs,
       ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / BG_WAVE;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) / BG_WAVE;
   for (int64_t j = wave_global; j < njobs; j += nwaves) {
-    const Lz4BlockJob job = jobs[j];
-    const int64_t r = lz4_compress_one(job.src, job.blen, job.dst_slot, tab);
+    const bg_lz4_block_job job = jobs[j];
+    const int64_t r =
+        lz4_compress_one(job.d_src, job.blen, job.d_dst_slot, tab);
     if (lane_id() == 0) block_sizes[j] = r;
   }
 }
 
-extern "C" int bg_lz4_compress_flat(const void* h_jobs, int64_t njobs,
-                                    int64_t* h_block_sizes) {
+extern "C" int bg_lz4_compress_flat(const bg_lz4_block_job* h_jobs,
+                                    int64_t njobs, int64_t* h_block_sizes) {
   REQUIRE_INIT();
-  DevBuf<Lz4BlockJob> d_jobs;
+  DevBuf<bg_lz4_block_job> d_jobs;
   DevBuf<int64_t> d_sizes;
   HIP_TRY(d_jobs.alloc(njobs));
   HIP_TRY(d_sizes.alloc(njobs));
-  HIP_TRY(hipMemcpy(d_jobs, h_jobs, sizeof(Lz4BlockJob) * njobs,
+  HIP_TRY(hipMemcpy(d_jobs, h_jobs, sizeof(bg_lz4_block_job) * njobs,
                     hipMemcpyHostToDevice));
   const int waves_per_block = BG_BLOCK / BG_WAVE;
   const size_t lds = (size_t)waves_per_block * (1 << LZ4_HASH_LOG) *
@@ -5944,7 +5838,7 @@ extern "C" int bg_lz4_compress(const void* d_src, int64_t len,
                                void* d_out_slots, int64_t* h_block_sizes,
                                int64_t* out_nblocks) {
   REQUIRE_INIT();
-  const int64_t nblocks = (len + LZ4_BLOCK - 1) / LZ4_BLOCK;
+  const int64_t nblocks = (len + BG_LZ4_BLOCK - 1) / BG_LZ4_BLOCK;
   DevBuf<int64_t> d_sizes;
   HIP_TRY(d_sizes.alloc(nblocks));
   const int waves_per_block = BG_BLOCK / BG_WAVE;
@@ -5953,7 +5847,7 @@ extern "C" int bg_lz4_compress(const void* d_src, int64_t len,
   int blocks = grid_for(nblocks, waves_per_block);
   hipLaunchKernelGGL(k_lz4_compress, dim3(blocks), dim3(BG_BLOCK), lds, 0,
                      (const uint8_t*)d_src, len, (uint8_t*)d_out_slots,
-                     (int64_t)LZ4_SLOT_STRIDE, d_sizes, nblocks);
+                     (int64_t)BG_LZ4_SLOT_STRIDE, d_sizes, nblocks);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(h_block_sizes, d_sizes, sizeof(int64_t) * nblocks,
                     hipMemcpyDeviceToHost));
@@ -5967,34 +5861,26 @@ extern "C" int bg_lz4_compress(const void* d_src, int64_t len,
 // host downloads ONE contiguous compressed stream per buffer (no
 // slot-strided D2H, no host-side slicing).
 // ---------------------------------------------------------------------------
-struct PackJob {
-  const uint8_t* src;
-  uint8_t* dst;        // points AT the 4-byte size word
-  int64_t nbytes;      // block payload bytes
-  uint32_t size_word;  // little-endian u32 (high bit = stored)
-  uint32_t _pad;
-};
-
-__global__ void k_pack_blocks(const PackJob* jobs, int64_t njobs) {
+__global__ void k_pack_blocks(const bg_pack_job* jobs, int64_t njobs) {
   for (int64_t j = blockIdx.x; j < njobs; j += gridDim.x) {
-    const PackJob job = jobs[j];
+    const bg_pack_job job = jobs[j];
     if (threadIdx.x == 0) {
-      job.dst[0] = (uint8_t)(job.size_word & 0xff);
-      job.dst[1] = (uint8_t)((job.size_word >> 8) & 0xff);
-      job.dst[2] = (uint8_t)((job.size_word >> 16) & 0xff);
-      job.dst[3] = (uint8_t)((job.size_word >> 24) & 0xff);
+      job.d_dst[0] = (uint8_t)(job.size_word & 0xff);
+      job.d_dst[1] = (uint8_t)((job.size_word >> 8) & 0xff);
+      job.d_dst[2] = (uint8_t)((job.size_word >> 16) & 0xff);
+      job.d_dst[3] = (uint8_t)((job.size_word >> 24) & 0xff);
     }
-    uint8_t* d = job.dst + 4;
+    uint8_t* d = job.d_dst + 4;
     for (int64_t i = threadIdx.x; i < job.nbytes; i += blockDim.x)
-      d[i] = job.src[i];
+      d[i] = job.d_src[i];
   }
 }
 
-extern "C" int bg_pack_blocks(const void* h_jobs, int64_t njobs) {
+extern "C" int bg_pack_blocks(const bg_pack_job* h_jobs, int64_t njobs) {
   REQUIRE_INIT();
-  DevBuf<PackJob> d_jobs;
+  DevBuf<bg_pack_job> d_jobs;
   HIP_TRY(d_jobs.alloc(njobs));
-  HIP_TRY(hipMemcpy(d_jobs, h_jobs, sizeof(PackJob) * njobs,
+  HIP_TRY(hipMemcpy(d_jobs, h_jobs, sizeof(bg_pack_job) * njobs,
                     hipMemcpyHostToDevice));
   int blocks = grid_for(njobs, 1);
   hipLaunchKernelGGL(k_pack_blocks, dim3(blocks), dim3(BG_BLOCK), 0, 0, d_jobs,
@@ -6303,23 +6189,16 @@ extern "C" int bg_hash_repartition_fused(const bg_column* key_cols,
 // Handles stored blocks (high-bit size) and linked or independent blocks
 // (the output is contiguous, so back-references past block starts work).
 // ---------------------------------------------------------------------------
-struct Lz4Frame {
-  const uint8_t* src;   // at the frame magic
-  uint8_t* dst;
-  int64_t src_len;
-  int64_t dst_cap;
-};
-
-__global__ void k_lz4_decompress(const Lz4Frame* frames, int64_t nframes,
+__global__ void k_lz4_decompress(const bg_lz4_frame* frames, int64_t nframes,
                                  int64_t* out_lens) {
   const int64_t wave_global =
       ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / BG_WAVE;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) / BG_WAVE;
   const int lane = lane_id();
   for (int64_t f = wave_global; f < nframes; f += nwaves) {
-    const uint8_t* s = frames[f].src;
+    const uint8_t* s = frames[f].d_src;
     const uint8_t* send = s + frames[f].src_len;
-    uint8_t* base_d = frames[f].dst;
+    uint8_t* base_d = frames[f].d_dst;
     const int64_t dcap = frames[f].dst_cap;
     int ok = 1;
     int64_t si = 0, di = 0;
@@ -6443,14 +6322,14 @@ __global__ void k_lz4_decompress(const Lz4Frame* frames, int64_t nframes,
   }
 }
 
-extern "C" int bg_lz4_decompress(const void* h_frames, int64_t nframes,
+extern "C" int bg_lz4_decompress(const bg_lz4_frame* h_frames, int64_t nframes,
                                  int64_t* h_out_lens) {
   REQUIRE_INIT();
-  DevBuf<Lz4Frame> d_frames;
+  DevBuf<bg_lz4_frame> d_frames;
   DevBuf<int64_t> d_lens;
   HIP_TRY(d_frames.alloc(nframes));
   HIP_TRY(d_lens.alloc(nframes));
-  HIP_TRY(hipMemcpy(d_frames, h_frames, sizeof(Lz4Frame) * nframes,
+  HIP_TRY(hipMemcpy(d_frames, h_frames, sizeof(bg_lz4_frame) * nframes,
                     hipMemcpyHostToDevice));
   const int waves_per_block = BG_BLOCK / BG_WAVE;
   int blocks = grid_for(nframes, waves_per_block);
@@ -6540,34 +6419,34 @@ __global__ void k_agg_materialize(const uint8_t* __restrict__ acc,
       }
     }
     switch (op) {
-      case BG_AGG_SUM_DEC128: {  // i128 LE, 16-B out
+      case BG_AGG_OP_SUM_DEC128: {  // i128 LE, 16-B out
         uint64_t* o = reinterpret_cast<uint64_t*>(out + g * 16);
         o[0] = is_null ? 0 : lo;
         o[1] = is_null ? 0 : hi;
         break;
       }
-      case BG_AGG_SUM_I64: {  // low limb as i64
+      case BG_AGG_OP_SUM_I64: {  // low limb as i64
         reinterpret_cast<int64_t*>(out)[g] = is_null ? 0 : (int64_t)lo;
         break;
       }
-      case BG_AGG_SUM_F64: {
+      case BG_AGG_OP_SUM_F64: {
         reinterpret_cast<uint64_t*>(out)[g] = is_null ? 0 : lo;
         break;
       }
-      case BG_AGG_MAX_I64: {
+      case BG_AGG_OP_MAX_I64: {
         reinterpret_cast<int64_t*>(out)[g] =
             is_null ? 0 : (int64_t)(lo ^ 0x8000000000000000ull);
         break;
       }
-      case BG_AGG_MIN_I64: {
+      case BG_AGG_OP_MIN_I64: {
         reinterpret_cast<int64_t*>(out)[g] =
             is_null ? 0 : (int64_t)((~lo) ^ 0x8000000000000000ull);
         break;
       }
-      case BG_AGG_MIN_F64:
-      case BG_AGG_MAX_F64: {
+      case BG_AGG_OP_MIN_F64:
+      case BG_AGG_OP_MAX_F64: {
         uint64_t enc = lo;
-        if (op == BG_AGG_MIN_F64) enc = ~enc;
+        if (op == BG_AGG_OP_MIN_F64) enc = ~enc;
         uint64_t bits = (enc >> 63) ? (enc ^ 0x8000000000000000ull) : ~enc;
         reinterpret_cast<uint64_t*>(out)[g] = is_null ? 0 : bits;
         break;

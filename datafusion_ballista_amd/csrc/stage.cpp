@@ -52,10 +52,9 @@
 #include <vector>
 
 #include "../../include/ballista_gpu.h"
+#include "bg_internal.h"
 #include "stage_ipc.h"
 #include "stage_json.h"
-
-extern "C" int bg_set_error(int code, const char* msg);
 
 namespace bgstage {
 
@@ -545,7 +544,7 @@ static Table read_shuffle_locations(const std::vector<Value*>& locations,
   for (auto& b : batches) {
     size_t bi = 0;
     for (size_t c = 0; c < ncols; ++c) {
-      auto add_frame = [&](const bgipc::BufSpec& sp, void* dst,
+      auto add_frame = [&](const bgipc::BufSpec& sp, uint8_t* dst,
                            int64_t dst_cap) {
         if (b.compressed) {
           // Arrow compressed-body convention: uncompressed-length prefix
@@ -569,7 +568,7 @@ static Table read_shuffle_locations(const std::vector<Value*>& locations,
       if (vsp.len > 0) {
         int64_t vu = real_usize(b, vsp);
         DBufPtr scr = dalloc((uint64_t)vu + 8);
-        add_frame(vsp, scr->p, vu + 8);
+        add_frame(vsp, scr->u8(), vu + 8);
         fixups.push_back({0, c, scr, b.rows, row_cursor, 0});
       }
       if (dts[c].dt == BG_DT_UTF8) {
@@ -577,7 +576,7 @@ static Table read_shuffle_locations(const std::vector<Value*>& locations,
         const auto& dsp = b.bufs[bi + 2];
         int64_t ou = real_usize(b, osp);
         DBufPtr oscr = dalloc((uint64_t)ou + 8);
-        add_frame(osp, oscr->p, ou + 8);
+        add_frame(osp, oscr->u8(), ou + 8);
         fixups.push_back({1, c, oscr, b.rows, row_cursor, utf8_cursor[c]});
         if (dsp.len > 0) {
           int64_t du = real_usize(b, dsp);
@@ -779,7 +778,7 @@ Col parquet_read_column(const uint8_t* h_file, size_t file_len,
       DBufPtr buf = dalloc((uint64_t)(d.ndict > 0 ? d.ndict : 1) *
                            (uint64_t)dst_esz);
       dict_bufs[kv.first] = buf;
-      dj.push_back({scratch->u8() + d.soff, buf->p, d.usz, d.ndict, src_esz,
+      dj.push_back({scratch->u8() + d.soff, buf->u8(), d.usz, d.ndict, src_esz,
                     0, is_flba ? 1 : 0, nullptr, nullptr});
       dj_rg.push_back(kv.first);
     }
@@ -2132,7 +2131,7 @@ static void write_consolidated(
                            nullptr /* set below */, payload, word, 0});
       // we cannot set d_dst before the packed buffer exists; record offset
       pack_jobs.back()._pad = 0;
-      pack_jobs.back().d_dst = (void*)(uintptr_t)off;  // offset placeholder
+      pack_jobs.back().d_dst = (uint8_t*)(uintptr_t)off;  // offset placeholder
       off += 4 + payload;
     }
     packed_cursor += off - packed_cursor;

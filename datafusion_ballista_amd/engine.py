@@ -17,7 +17,6 @@ Device work (hash, partition split, gather) runs through libballista_gpu.so;
 IPC encode + file write stay host-side.
 """
 
-import ctypes as _ct
 import time
 from dataclasses import dataclass
 
@@ -221,8 +220,7 @@ class GpuQueryStageExecutor:
         for i in null_ids:
             ob = ctx.alloc(max(((n + 63) // 64) * 8, 8))
             gpu._check(ctx.L.bg_gather_bits(
-                _ct.c_void_p(cols[i].d_validity), idx_buf.ptr,
-                _ct.c_int64(n), ob.ptr), "bg_gather_bits")
+                cols[i].d_validity, idx_buf.ptr, n, ob.ptr), "bg_gather_bits")
             valid_out[i] = ob
         ctx.synchronize()
         dt_device = time.perf_counter() - t_repart
@@ -326,9 +324,9 @@ def _encode_partitions_gpu(self, schema, offsets, cols, out_bufs,
     contribute rebased i32 offsets (bg_sub_i32 on device) + their byte
     range; null columns ride as host-LZ4'd validity parts (1/64 of the
     data bytes, already host-resident for metrics)."""
-    import ctypes
     import struct
     ctx = self.ctx
+    BLOCK = gpu.BG_LZ4_BLOCK
     valid_perm = valid_perm or {}
     utf8_out = utf8_out or {}
     utf8_raws = utf8_raws or {}
@@ -349,9 +347,8 @@ def _encode_partitions_gpu(self, schema, offsets, cols, out_bufs,
             if m == 0:
                 continue
             gpu._check(ctx.L.bg_sub_i32(
-                ctypes.c_void_p(oo.ptr.value + 4 * lo),
-                ctypes.c_int64(m + 1), ctypes.c_int32(int(offs_all[lo])),
-                ctypes.c_void_p(r.ptr.value + 4 * cur)), "bg_sub_i32")
+                oo.at(4 * lo), m + 1, int(offs_all[lo]), r.at(4 * cur)),
+                "bg_sub_i32")
             regions[p] = cur
             cur += m + 1
         reb[ci] = (r, regions)
@@ -371,31 +368,27 @@ def _encode_partitions_gpu(self, schema, offsets, cols, out_bufs,
                 offs_all = utf8_raws[ci][0]
                 r, regions = reb[ci]
                 o_lo, o_hi = int(offs_all[lo]), int(offs_all[hi])
-                units = [("offs", r.ptr.value + 4 * regions[p],
-                          4 * (m + 1)),
-                         ("data", od.ptr.value + o_lo, o_hi - o_lo)]
+                units = [("offs", r.at(4 * regions[p]), 4 * (m + 1)),
+                         ("data", od.at(o_lo), o_hi - o_lo)]
             else:
                 esz = gpu._DT_SIZE[cols[ci].dtype]
-                units = [("data", fixed_buf[ci].ptr.value + lo * esz,
-                          m * esz)]
+                units = [("data", fixed_buf[ci].at(lo * esz), m * esz)]
             for kind, src_ptr, length in units:
-                nblocks = (length + 65536 - 1) // 65536
+                nblocks = (length + BLOCK - 1) // BLOCK
                 buf_meta.append((p, ci, kind, length, nblocks, len(jobs)))
                 for i in range(nblocks):
-                    blen = min(65536, length - i * 65536)
-                    jobs.append((src_ptr + i * 65536, slot_cursor, blen))
-                    slot_cursor += 65544
+                    blen = min(BLOCK, length - i * BLOCK)
+                    jobs.append((src_ptr + i * BLOCK, slot_cursor, blen))
+                    slot_cursor += gpu.BG_LZ4_SLOT_STRIDE
     if not jobs:
         return [b""] * self.k
     slots = ctx.alloc(max(slot_cursor, 8))
     jarr = (gpu.BgLz4BlockJob * len(jobs))()
     for i, (src, soff, blen) in enumerate(jobs):
-        jarr[i] = gpu.BgLz4BlockJob(src, slots.ptr.value + soff, blen, 0)
+        jarr[i] = gpu.BgLz4BlockJob(src, slots.at(soff), blen, 0)
     sizes = np.zeros(len(jobs), dtype=np.int64)
-    gpu._check(ctx.L.bg_lz4_compress_flat(
-        jarr, ctypes.c_int64(len(jobs)),
-        sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
-        "bg_lz4_compress_flat")
+    gpu._check(ctx.L.bg_lz4_compress_flat(jarr, len(jobs), sizes.ctypes.data),
+               "bg_lz4_compress_flat")
 
     # phase 2: pack each buffer's [u32 size][block] sequence contiguously
     pack_jobs = []
@@ -411,7 +404,7 @@ def _encode_partitions_gpu(self, schema, offsets, cols, out_bufs,
         off = packed_cursor
         for i in range(nblocks):
             sz = int(sizes[job0 + i])
-            blen = min(65536, length - i * 65536)
+            blen = min(BLOCK, length - i * BLOCK)
             payload = blen if sz < 0 else sz
             word = (blen | 0x80000000) if sz < 0 else sz
             pack_jobs.append((jobs[job0 + i][1], off, payload, word))
@@ -420,10 +413,9 @@ def _encode_partitions_gpu(self, schema, offsets, cols, out_bufs,
     packed = ctx.alloc(max(packed_cursor, 8))
     parr = (gpu.BgPackJob * len(pack_jobs))()
     for i, (soff, doff, payload, word) in enumerate(pack_jobs):
-        parr[i] = gpu.BgPackJob(slots.ptr.value + soff,
-                                packed.ptr.value + doff, payload, word, 0)
-    gpu._check(ctx.L.bg_pack_blocks(parr, ctypes.c_int64(len(pack_jobs))),
-               "bg_pack_blocks")
+        parr[i] = gpu.BgPackJob(slots.at(soff), packed.at(doff), payload,
+                                word, 0)
+    gpu._check(ctx.L.bg_pack_blocks(parr, len(pack_jobs)), "bg_pack_blocks")
 
     # phase 3: one D2H of the whole packed region, then assemble streams
     packed_host = packed.download(np.uint8, packed_cursor).tobytes()

@@ -3,6 +3,11 @@
 The GpuStageContext owns device memory for one task's columns and exposes
 the hot-path ops.  It fails loudly (RuntimeError) when the HIP extension or
 the GPU is missing — no CPU fallback exists on the product path.
+
+The ABI is stated once here — the constants, the struct classes and the
+_SIGNATURES table below — and tests/test_cabi.py checks all three against
+the header.  load_library() applies the table as argtypes/restype, so call
+sites pass plain Python ints for 64-bit parameters.
 """
 
 import ctypes
@@ -11,13 +16,9 @@ import struct as _struct
 
 import numpy as np
 
-
-def struct_unpack_bits(v: float) -> int:
-    """f64 -> its bit pattern as a SIGNED i64 (BgPred bound fields)."""
-    return _struct.unpack("<q", _struct.pack("<d", v))[0]
-
 _DIR = os.path.dirname(os.path.abspath(__file__))
 
+# ---- constants (mirror include/ballista_gpu.h) ----
 BG_DT_INT32 = 1
 BG_DT_INT64 = 2
 BG_DT_DATE32 = 3
@@ -32,6 +33,25 @@ BG_PRED_LT = 2
 BG_PRED_EQ = 3
 BG_PRED_GT = 4
 
+BG_AGG_OP_SUM_DEC128 = 0
+BG_AGG_OP_SUM_I64 = 1
+BG_AGG_OP_MIN_I64 = 2
+BG_AGG_OP_MAX_I64 = 3
+BG_AGG_OP_SUM_F64 = 4
+BG_AGG_OP_MIN_F64 = 5
+BG_AGG_OP_MAX_F64 = 6
+
+BG_PROJ_MUL = 0
+BG_PROJ_ADD = 1
+BG_PROJ_SUB = 2
+BG_PROJ_RSUB_LIT = 3
+BG_PROJ_MUL_LIT = 4
+BG_PROJ_ADD_LIT = 5
+
+BG_LZ4_BLOCK = 65536
+BG_LZ4_SLOT_STRIDE = 65544
+LZ4_FRAME_HEADER = bytes.fromhex("04224d184040c0")  # magic+FLG+BD+HC
+
 _DT_SIZE = {BG_DT_INT32: 4, BG_DT_DATE32: 4, BG_DT_INT64: 8,
             BG_DT_DECIMAL128: 16, BG_DT_DICT8: 1, BG_DT_FLOAT64: 8}
 
@@ -42,29 +62,143 @@ _NP_TO_DT = {
     np.dtype(np.float64): BG_DT_FLOAT64,
 }
 
+# ---- structs: class BgFooBar mirrors the header's bg_foo_bar ----
+_p, _i32, _u32, _i64 = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32,
+                        ctypes.c_int64)
+
 
 class BgColumn(ctypes.Structure):
-    _fields_ = [
-        ("dtype", ctypes.c_int32),
-        ("precision", ctypes.c_int32),
-        ("scale", ctypes.c_int32),
-        ("_pad", ctypes.c_int32),
-        ("d_data", ctypes.c_void_p),
-        ("d_validity", ctypes.c_void_p),
-        ("d_offsets", ctypes.c_void_p),
-        ("len", ctypes.c_int64),
-    ]
+    _fields_ = [("dtype", _i32), ("precision", _i32), ("scale", _i32),
+                ("_pad", _i32), ("d_data", _p), ("d_validity", _p),
+                ("d_offsets", _p), ("len", _i64)]
 
 
 class BgPred(ctypes.Structure):
-    _fields_ = [
-        ("column", ctypes.c_int32),
-        ("op", ctypes.c_int32),
-        ("lo_lo", ctypes.c_int64),
-        ("lo_hi", ctypes.c_int64),
-        ("hi_lo", ctypes.c_int64),
-        ("hi_hi", ctypes.c_int64),
-    ]
+    _fields_ = [("column", _i32), ("op", _i32), ("lo_lo", _i64),
+                ("lo_hi", _i64), ("hi_lo", _i64), ("hi_hi", _i64)]
+
+
+class BgSnappyPage(ctypes.Structure):
+    _fields_ = [("d_src", _p), ("d_dst", _p), ("src_len", _i64),
+                ("dst_cap", _i64)]
+
+
+class BgPageExtractJob(ctypes.Structure):
+    _fields_ = [("d_page", _p), ("d_out", _p), ("page_len", _i64),
+                ("nvals", _i64), ("src_esz", _i64), ("has_def", _i32),
+                ("flba_reverse", _i32), ("d_vidx", _p), ("d_n_present", _p)]
+
+
+class BgDictIndicesJob(ctypes.Structure):
+    _fields_ = [("d_page", _p), ("d_out_idx", _p), ("page_len", _i64),
+                ("nvals", _i64), ("has_def", _i32), ("_pad", _i32),
+                ("d_vidx", _p), ("d_n_present", _p), ("d_dense", _p)]
+
+
+class BgDefLevelsJob(ctypes.Structure):
+    _fields_ = [("d_page", _p), ("d_vidx", _p), ("d_valid_out", _p),
+                ("page_len", _i64), ("nvals", _i64), ("bit_off", _i64),
+                ("d_n_present", _p)]
+
+
+class BgListLevelsJob(ctypes.Structure):
+    _fields_ = [("d_page", _p), ("page_len", _i64), ("nslots", _i64),
+                ("max_def", _i32), ("def_entry", _i32), ("def_valid", _i32),
+                ("_pad", _i32), ("row_base", _i64), ("entry_base", _i64),
+                ("d_counts", _p), ("d_row_sizes", _p), ("d_list_valid", _p),
+                ("d_elem_valid", _p), ("d_vidx", _p)]
+
+
+class BgBaPageJob(ctypes.Structure):
+    _fields_ = [("d_page", _p), ("d_lens_out", _p), ("d_srcaddr_out", _p),
+                ("page_len", _i64), ("nvals", _i64), ("has_def", _i32),
+                ("_pad", _i32), ("d_vidx", _p), ("d_n_present", _p)]
+
+
+class BgDeltaBpJob(ctypes.Structure):
+    _fields_ = [("d_page", _p), ("d_out", _p), ("page_len", _i64),
+                ("nvals", _i64), ("esz", _i64), ("has_def", _i32),
+                ("_pad", _i32), ("d_vidx", _p), ("d_n_present", _p)]
+
+
+class BgDeltaBaJob(ctypes.Structure):
+    _fields_ = [("d_page", _p), ("d_lens_out", _p), ("d_srcaddr_out", _p),
+                ("d_offs32", _p), ("d_data_out", _p), ("page_len", _i64),
+                ("nvals", _i64), ("has_def", _i32), ("enc", _i32),
+                ("d_vidx", _p), ("d_n_present", _p)]
+
+
+class BgLz4BlockJob(ctypes.Structure):
+    _fields_ = [("d_src", _p), ("d_dst_slot", _p), ("blen", _i32),
+                ("_pad", _i32)]
+
+
+class BgLz4Frame(ctypes.Structure):
+    _fields_ = [("d_src", _p), ("d_dst", _p), ("src_len", _i64),
+                ("dst_cap", _i64)]
+
+
+class BgPackJob(ctypes.Structure):
+    _fields_ = [("d_src", _p), ("d_dst", _p), ("nbytes", _i64),
+                ("size_word", _u32), ("_pad", _u32)]
+
+
+# ---- function signatures: "<return> <one code per parameter>" ----
+# Every data pointer is a c_void_p, which takes None, an int address, a
+# c_void_p, byref(...), a ctypes array or a POINTER instance alike.
+_CODES = {
+    "v": None,
+    "i": ctypes.c_int32, "u": ctypes.c_uint32,
+    "l": ctypes.c_int64, "L": ctypes.c_uint64,
+    "d": ctypes.c_double,
+    "p": ctypes.c_void_p,                  # any data pointer
+    "s": ctypes.c_char_p,                  # [const] char*
+    "S": ctypes.POINTER(ctypes.c_char_p),  # char** / const char* const*
+    "P": ctypes.POINTER(ctypes.c_void_p),  # void** / void* const*
+}
+
+_SIGNATURES = {
+    "bg_last_error": "s", "bg_version": "i", "bg_source_hash": "s",
+    "bg_last_kernel_ms": "d", "bg_init": "i i", "bg_device_count": "i p",
+    "bg_synchronize": "i", "bg_malloc": "i LP", "bg_free": "i p",
+    "bg_memset": "i piL", "bg_memcpy_h2d": "i ppL", "bg_memcpy_d2h": "i ppL",
+    "bg_memcpy_dtod": "i ppL", "bg_pool_trim": "i", "bg_pool_stats": "i ppp",
+    "bg_eval_predicates": "i pipilp", "bg_mask_to_indices": "i plpp",
+    "bg_gather": "i plplp", "bg_gather_varlen": "i ppplpplp",
+    "bg_sub_i32": "i plip", "bg_gather_bits": "i pplp",
+    "bg_eval_like": "i pSpiiiilp", "bg_select": "i pppllp",
+    "bg_fill_const": "i pllll", "bg_eval_in": "i ppilp",
+    "bg_bitmap_or": "i pplp", "bg_hash_columns": "i pilp",
+    "bg_partition_ids": "i plup", "bg_partition_indices": "i plupp",
+    "bg_partition_indices_ex": "i pluppp", "bg_scatter_rows": "i plplp",
+    "bg_hash_repartition": "i pipiluppP", "bg_hashjoin_build": "i plP",
+    "bg_hashjoin_probe_count": "i pplp", "bg_hashjoin_probe_fill": "i pplpp",
+    "bg_hashjoin_free": "i p", "bg_hashjoin_build2": "i pilP",
+    "bg_hashjoin_probe_count2": "i ppilip",
+    "bg_hashjoin_probe_fill2": "i ppilipp", "bg_hashjoin_free2": "i p",
+    "bg_idx_sentinel": "i plpp", "bg_bitmap_and": "i pplp",
+    "bg_hashagg": "i pippipllpppp", "bg_hashagg2": "i pippipllppppp",
+    "bg_project_dec128": "i ipplllp",
+    "bg_project_dec128_multi": "i pippipippilP", "bg_sort_rows": "i ppilp",
+    "bg_sort_rows2": "i pppilp", "bg_merge_join": "i plplppp",
+    "bg_snappy_decompress": "i plp", "bg_page_extract": "i plplllii",
+    "bg_dict_indices": "i pllip", "bg_page_extract_batch": "i pl",
+    "bg_dict_indices_batch": "i pl", "bg_def_levels_batch": "i pl",
+    "bg_list_levels_batch": "i pli", "bg_ba_extract_batch": "i pl",
+    "bg_ba_from_dict": "i pppplpp", "bg_ba_materialize": "i pplpplp",
+    "bg_delta_bp_batch": "i pl", "bg_delta_ba_batch": "i pli",
+    "bg_bss_batch": "i pl", "bg_lz4_compress": "i plppp",
+    "bg_lz4_compress_flat": "i plp", "bg_lz4_decompress": "i plp",
+    "bg_pack_blocks": "i pl", "bg_hash_repartition_fused": "i pipilupppP",
+    "bg_bitcopy": "i plpl", "bg_agg_materialize": "i plilpplp",
+    "bg_copy_i64_strided": "i pllp", "bg_avg_finalize": "i pliplilpp",
+    "bg_execute_stage": "i sS", "bg_stage_free": "v s",
+    "bg_stage_validate": "i sS", "bg_stage_register_table": "i spSil",
+    "bg_stage_unregister_table": "i s", "bg_fill_rand": "i plLlli",
+    "bg_q6_agg": "i ppppiilllppp", "bg_q1_agg": "i pppppppipp",
+    # csrc/bg_internal.h (exported, not public API)
+    "bg_set_error": "i is", "bg_debug_rb_message": "i lpipiliS",
+}
 
 
 def lib_path() -> str:
@@ -75,7 +209,8 @@ _lib = None
 
 
 def load_library() -> ctypes.CDLL:
-    """dlopen the HIP extension; raises if it is absent or unloadable."""
+    """dlopen the HIP extension and declare every entry point's signature;
+    raises if the library is absent or unloadable."""
     global _lib
     if _lib is None:
         p = lib_path()
@@ -84,9 +219,12 @@ def load_library() -> ctypes.CDLL:
                 f"libballista_gpu.so not found at {p}: the MI355X stage "
                 "executor requires its HIP extension (run "
                 "__graft_entry__.build()); there is no CPU fallback")
-        _lib = ctypes.CDLL(p)
-        _lib.bg_last_error.restype = ctypes.c_char_p
-        _lib.bg_last_kernel_ms.restype = ctypes.c_double
+        lib = ctypes.CDLL(p)
+        for name, sig in _SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = _CODES[sig[0]]
+            fn.argtypes = [_CODES[c] for c in sig[2:]]
+        _lib = lib
     return _lib
 
 
@@ -96,10 +234,52 @@ def _check(rc: int, what: str):
         raise RuntimeError(f"{what} failed (rc={rc}): {err}")
 
 
+def struct_unpack_bits(v: float) -> int:
+    """f64 -> its bit pattern as a SIGNED i64 (BgPred bound fields)."""
+    return _struct.unpack("<q", _struct.pack("<d", v))[0]
+
+
 def _split_i128(v: int):
     v = int(v)
     return (ctypes.c_int64(v & 0xFFFFFFFFFFFFFFFF).value,
             ctypes.c_int64((v >> 64) & 0xFFFFFFFFFFFFFFFF).value)
+
+
+def decode_agg_value(op, raw16: bytes):
+    """Accumulator bytes -> python int/float per aggregate op."""
+    if op in (BG_AGG_OP_SUM_DEC128, BG_AGG_OP_SUM_I64):
+        return int.from_bytes(raw16, "little", signed=True)
+    if op == BG_AGG_OP_SUM_F64:
+        return _struct.unpack("<d", raw16[:8])[0]
+    enc = int.from_bytes(raw16[:8], "little")
+    if op in (BG_AGG_OP_MIN_F64, BG_AGG_OP_MAX_F64):
+        if op == BG_AGG_OP_MIN_F64:
+            enc = ~enc & 0xFFFFFFFFFFFFFFFF
+        bits = (~enc & 0xFFFFFFFFFFFFFFFF) if not (enc >> 63) \
+            else enc ^ (1 << 63)
+        return _struct.unpack("<d", _struct.pack("<Q", bits))[0]
+    if op == BG_AGG_OP_MAX_I64:
+        v = enc ^ (1 << 63)
+    else:  # MIN_I64
+        v = (~enc & 0xFFFFFFFFFFFFFFFF) ^ (1 << 63)
+    return v - (1 << 64) if v >= 1 << 63 else v
+
+
+def lz4_frame_assemble(sizes, slot_bytes: bytes, length: int) -> bytes:
+    """Host glue: device block slots -> one LZ4 frame (constant header,
+    [u32 size] blocks — high bit = stored — end mark)."""
+    out = [LZ4_FRAME_HEADER]
+    for i, sz in enumerate(sizes):
+        base = i * BG_LZ4_SLOT_STRIDE
+        blen = min(BG_LZ4_BLOCK, length - i * BG_LZ4_BLOCK)
+        if sz < 0:  # stored raw
+            out.append(_struct.pack("<I", blen | 0x80000000))
+            out.append(slot_bytes[base:base + blen])
+        else:
+            out.append(_struct.pack("<I", int(sz)))
+            out.append(slot_bytes[base:base + int(sz)])
+    out.append(b"\x00\x00\x00\x00")
+    return b"".join(out)
 
 
 class DeviceBuffer:
@@ -110,9 +290,13 @@ class DeviceBuffer:
         self._owns = True
         self.nbytes = nbytes
         ptr = ctypes.c_void_p()
-        _check(ctx.L.bg_malloc(ctypes.c_uint64(nbytes), ctypes.byref(ptr)),
-               "bg_malloc")
+        _check(ctx.L.bg_malloc(nbytes, ctypes.byref(ptr)), "bg_malloc")
         self.ptr = ptr
+
+    def at(self, byte_off: int) -> int:
+        """Device address `byte_off` bytes into the buffer, as an int (what
+        a pointer parameter or a job struct's pointer field takes)."""
+        return self.ptr.value + byte_off
 
     def free(self):
         if self.ptr and self.ptr.value:
@@ -136,16 +320,14 @@ class DeviceBuffer:
     def upload(self, arr: np.ndarray):
         a = np.ascontiguousarray(arr)
         assert a.nbytes <= self.nbytes
-        _check(self._ctx.L.bg_memcpy_h2d(
-            self.ptr, a.ctypes.data_as(ctypes.c_void_p),
-            ctypes.c_uint64(a.nbytes)), "bg_memcpy_h2d")
+        _check(self._ctx.L.bg_memcpy_h2d(self.ptr, a.ctypes.data, a.nbytes),
+               "bg_memcpy_h2d")
         return self
 
     def download(self, dtype, count) -> np.ndarray:
         out = np.empty(count, dtype=dtype)
-        _check(self._ctx.L.bg_memcpy_d2h(
-            out.ctypes.data_as(ctypes.c_void_p), self.ptr,
-            ctypes.c_uint64(out.nbytes)), "bg_memcpy_d2h")
+        _check(self._ctx.L.bg_memcpy_d2h(out.ctypes.data, self.ptr,
+                                         out.nbytes), "bg_memcpy_d2h")
         return out
 
 
@@ -156,7 +338,6 @@ class GpuStageContext:
     def __init__(self, device: int = 0):
         self.L = load_library()
         _check(self.L.bg_init(device), "bg_init")
-        self._bufs = []
 
     # ---- memory ----
     def alloc(self, nbytes: int) -> DeviceBuffer:
@@ -171,7 +352,7 @@ class GpuStageContext:
         return self.alloc(arr.nbytes).upload(arr)
 
     def close(self):
-        self._bufs = []  # legacy; buffers free themselves via __del__
+        pass  # buffers free themselves via DeviceBuffer.__del__
 
     def synchronize(self):
         _check(self.L.bg_synchronize(), "bg_synchronize")
@@ -217,7 +398,7 @@ class GpuStageContext:
         n = arr.nbytes // _DT_SIZE[dtype]
         return self.column(dtype, buf, n, vbuf), buf
 
-    # ---- ops ----
+    # ---- filter / gather ----
     def eval_predicates(self, cols, preds, n: int) -> DeviceBuffer:
         """cols: list[BgColumn]; preds: list[(col, op, lo, hi)] with python
         int bounds. Returns the device mask (ceil(n/64)*8 bytes)."""
@@ -235,14 +416,13 @@ class GpuStageContext:
             hi_lo, hi_hi = _split_i128(hi)
             parr[i] = BgPred(c, op, lo_lo, lo_hi, hi_lo, hi_hi)
         _check(self.L.bg_eval_predicates(carr, len(cols), parr, len(preds),
-                                         ctypes.c_int64(n), mask.ptr),
-               "bg_eval_predicates")
+                                         n, mask.ptr), "bg_eval_predicates")
         return mask
 
     def mask_to_indices(self, mask: DeviceBuffer, n: int):
         idx = self.alloc(max(4 * n, 4))
         count = ctypes.c_int64()
-        _check(self.L.bg_mask_to_indices(mask.ptr, ctypes.c_int64(n), idx.ptr,
+        _check(self.L.bg_mask_to_indices(mask.ptr, n, idx.ptr,
                                          ctypes.byref(count)),
                "bg_mask_to_indices")
         return idx, count.value
@@ -250,51 +430,80 @@ class GpuStageContext:
     def gather(self, src: DeviceBuffer, elem_size: int, idx: DeviceBuffer,
                m: int) -> DeviceBuffer:
         dst = self.alloc(max(elem_size * m, elem_size))
-        _check(self.L.bg_gather(src.ptr, ctypes.c_int64(elem_size), idx.ptr,
-                                ctypes.c_int64(m), dst.ptr), "bg_gather")
+        _check(self.L.bg_gather(src.ptr, elem_size, idx.ptr, m, dst.ptr),
+               "bg_gather")
         return dst
 
+    def gather_varlen(self, src_data: DeviceBuffer, src_offsets: DeviceBuffer,
+                      idx: DeviceBuffer, m: int, max_bytes: int):
+        """Variable-length take -> (offsets buf i32[m+1], data buf, total)."""
+        out_offs = self.alloc(max(4 * (m + 1), 8))
+        out_data = self.alloc(max(max_bytes, 1))
+        total = ctypes.c_int64()
+        _check(self.L.bg_gather_varlen(src_data.ptr, src_offsets.ptr, idx.ptr,
+                                       m, out_offs.ptr, out_data.ptr,
+                                       max_bytes, ctypes.byref(total)),
+               "bg_gather_varlen")
+        return out_offs, out_data, total.value
+
+    # ---- hash repartition ----
     def hash_columns(self, key_cols, n: int) -> DeviceBuffer:
         hashes = self.alloc(max(8 * n, 8))
         karr = (BgColumn * len(key_cols))(*key_cols)
-        _check(self.L.bg_hash_columns(karr, len(key_cols), ctypes.c_int64(n),
-                                      hashes.ptr), "bg_hash_columns")
+        _check(self.L.bg_hash_columns(karr, len(key_cols), n, hashes.ptr),
+               "bg_hash_columns")
         return hashes
 
     def partition_ids(self, hashes: DeviceBuffer, n: int, k: int) -> DeviceBuffer:
         pids = self.alloc(max(4 * n, 4))
-        _check(self.L.bg_partition_ids(hashes.ptr, ctypes.c_int64(n), k,
-                                       pids.ptr), "bg_partition_ids")
+        _check(self.L.bg_partition_ids(hashes.ptr, n, k, pids.ptr),
+               "bg_partition_ids")
         return pids
 
     def partition_indices(self, pids: DeviceBuffer, n: int, k: int):
         idx = self.alloc(max(4 * n, 4))
         offs = self.alloc(8 * (k + 1))
-        _check(self.L.bg_partition_indices(pids.ptr, ctypes.c_int64(n), k,
-                                           idx.ptr, offs.ptr),
+        _check(self.L.bg_partition_indices(pids.ptr, n, k, idx.ptr, offs.ptr),
                "bg_partition_indices")
         return idx, offs
+
+    def _payload_outs(self, payload_cols, n: int):
+        """One partition-major output buffer per payload column, plus the
+        void*[ncols] the repartition entry points take."""
+        outs = []
+        for c in payload_cols:
+            esz = _DT_SIZE[c.dtype]
+            outs.append(self.alloc(max(esz * n, esz)))
+        optrs = (ctypes.c_void_p * len(outs))(*[b.ptr.value for b in outs])
+        return outs, optrs
 
     def hash_repartition(self, key_cols, payload_cols, n: int, k: int):
         """-> (indices buf, offsets buf, [out bufs partition-major])."""
         idx = self.alloc(max(4 * n, 4))
         offs = self.alloc(8 * (k + 1))
-        outs = []
-        optrs = (ctypes.c_void_p * len(payload_cols))()
-        for i, c in enumerate(payload_cols):
-            esz = _DT_SIZE[c.dtype]
-            b = self.alloc(max(esz * n, esz))
-            outs.append(b)
-            optrs[i] = b.ptr.value
+        outs, optrs = self._payload_outs(payload_cols, n)
         karr = (BgColumn * len(key_cols))(*key_cols)
         parr = (BgColumn * len(payload_cols))(*payload_cols)
-        _check(self.L.bg_hash_repartition(karr, len(key_cols), parr,
-                                          len(payload_cols),
-                                          ctypes.c_int64(n), k, idx.ptr,
-                                          offs.ptr, optrs),
-               "bg_hash_repartition")
+        _check(self.L.bg_hash_repartition(
+            karr, len(key_cols), parr, len(payload_cols), n, k, idx.ptr,
+            offs.ptr, optrs), "bg_hash_repartition")
         return idx, offs, outs
 
+    def hash_repartition_fused(self, key_cols, payload_cols, n: int, k: int):
+        """Fused one-pass materialiser (k<=64, <=4 fixed-width payload
+        cols): same outputs/stable order as hash_repartition."""
+        idx = self.alloc(max(4 * n, 4))
+        offs = self.alloc(8 * (k + 1))
+        rank = self.alloc(max(4 * n, 4))
+        outs, optrs = self._payload_outs(payload_cols, n)
+        karr = (BgColumn * len(key_cols))(*key_cols)
+        parr = (BgColumn * len(payload_cols))(*payload_cols)
+        _check(self.L.bg_hash_repartition_fused(
+            karr, len(key_cols), parr, len(payload_cols), n, k, idx.ptr,
+            offs.ptr, rank.ptr, optrs), "bg_hash_repartition_fused")
+        return idx, offs, outs
+
+    # ---- aggregate / project / sort / join ----
     def q6_agg(self, shipdate: BgColumn, discount: BgColumn,
                quantity: BgColumn, price: BgColumn, date_lo: int, date_hi: int,
                disc_lo: int, disc_hi: int, qty_lt: int):
@@ -304,11 +513,9 @@ class GpuStageContext:
         cnt = ctypes.c_int64()
         _check(self.L.bg_q6_agg(ctypes.byref(shipdate), ctypes.byref(discount),
                                 ctypes.byref(quantity), ctypes.byref(price),
-                                date_lo, date_hi,
-                                ctypes.c_int64(disc_lo), ctypes.c_int64(disc_hi),
-                                ctypes.c_int64(qty_lt), ctypes.byref(s_lo),
-                                ctypes.byref(s_hi), ctypes.byref(cnt)),
-               "bg_q6_agg")
+                                date_lo, date_hi, disc_lo, disc_hi, qty_lt,
+                                ctypes.byref(s_lo), ctypes.byref(s_hi),
+                                ctypes.byref(cnt)), "bg_q6_agg")
         return cnt.value, (s_hi.value << 64) + s_lo.value
 
     def q1_agg(self, rf, ls, qty, price, disc, tax, shipdate, date_le: int):
@@ -318,9 +525,8 @@ class GpuStageContext:
         _check(self.L.bg_q1_agg(
             ctypes.byref(rf), ctypes.byref(ls), ctypes.byref(qty),
             ctypes.byref(price), ctypes.byref(disc), ctypes.byref(tax),
-            ctypes.byref(shipdate), date_le,
-            counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-            sums.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))), "bg_q1_agg")
+            ctypes.byref(shipdate), date_le, counts.ctypes.data,
+            sums.ctypes.data), "bg_q1_agg")
         out = {}
         raw = sums.reshape(256, 5, 16)
         for g in range(256):
@@ -331,6 +537,122 @@ class GpuStageContext:
             out[g] = (int(counts[g]), vals)
         return out
 
+    def hashagg(self, key_cols, agg_cols, agg_ops, n, max_groups,
+                mask: DeviceBuffer = None, want_nncnt: bool = False):
+        """General hash group-by. -> (first_row u32[g], acc i128 bytes
+        [g, naggs], counts i64[g]) as numpy arrays (downloaded); with
+        want_nncnt also the per-(group, agg) NON-NULL input counts
+        i64[g, naggs] (SQL: SUM/MIN/MAX of an all-NULL group is NULL —
+        nncnt 0 marks it)."""
+        naggs = len(agg_cols)
+        karr = (BgColumn * len(key_cols))(*key_cols)
+        aarr = (BgColumn * max(naggs, 1))(*(agg_cols or [BgColumn()]))
+        oarr = (ctypes.c_int32 * max(naggs, 1))(*(agg_ops or [0]))
+        ng = ctypes.c_int64()
+        # auto-grow on table-full (the scheduler's row estimates can be low,
+        # like the reference's AQE-fed group estimates); the output buffers
+        # grow with the group capacity
+        cap = max_groups
+        for _ in range(8):
+            first = self.alloc(max(4 * cap, 4))
+            acc = self.alloc(max(16 * cap * max(naggs, 1), 16))
+            counts = self.alloc(max(8 * cap, 8))
+            args = [karr, len(key_cols), aarr, oarr, naggs,
+                    mask.ptr if mask else None, n, cap, first.ptr, acc.ptr,
+                    counts.ptr]
+            if want_nncnt:
+                nncnt = self.alloc(max(8 * cap * max(naggs, 1), 8))
+                rc = self.L.bg_hashagg2(*args, nncnt.ptr, ctypes.byref(ng))
+            else:
+                rc = self.L.bg_hashagg(*args, ctypes.byref(ng))
+            if rc == 0:
+                break
+            err = self.L.bg_last_error().decode()
+            if "table full" not in err or cap >= n:
+                _check(rc, "bg_hashagg")
+            cap = min(max(cap * 8, 64), max(n, 64))
+        else:
+            _check(rc, "bg_hashagg")
+        g = ng.value
+        ret = (first.download(np.uint32, g),
+               acc.download(np.uint8, 16 * g * naggs).reshape(g, naggs, 16)
+               if naggs else np.zeros((g, 0, 16), dtype=np.uint8),
+               counts.download(np.int64, g))
+        if want_nncnt:
+            nn = nncnt.download(np.int64, g * naggs).reshape(g, naggs) \
+                if naggs else np.zeros((g, 0), dtype=np.int64)
+            return ret + (nn,)
+        return ret
+
+    def project_dec128(self, op, a: BgColumn, b: BgColumn, lit, n):
+        out = self.alloc(max(16 * n, 16))
+        lo, hi = _split_i128(lit)
+        _check(self.L.bg_project_dec128(op, ctypes.byref(a),
+                                        ctypes.byref(b) if b else None,
+                                        lo, hi, n, out.ptr),
+               "bg_project_dec128")
+        return out
+
+    def sort_rows(self, key_cols, descending, n):
+        """Stable multi-column ORDER BY -> row permutation DeviceBuffer."""
+        perm = self.alloc(max(4 * n, 4))
+        karr = (BgColumn * len(key_cols))(*key_cols)
+        darr = (ctypes.c_int32 * len(key_cols))(*[1 if d else 0
+                                                  for d in descending])
+        _check(self.L.bg_sort_rows(karr, darr, len(key_cols), n, perm.ptr),
+               "bg_sort_rows")
+        return perm
+
+    def merge_join(self, build_sorted: DeviceBuffer, nb: int,
+                   probe_sorted: DeviceBuffer, np_: int):
+        """Inner merge join of key-sorted i64 buffers -> (probe_pos,
+        build_pos DeviceBuffers into the sorted orders, n_matches)."""
+        matches = ctypes.c_int64()
+        _check(self.L.bg_merge_join(build_sorted.ptr, nb, probe_sorted.ptr,
+                                    np_, ctypes.byref(matches), None, None),
+               "bg_merge_join(count)")
+        m = matches.value
+        pbuf = self.alloc(max(4 * m, 4))
+        bbuf = self.alloc(max(4 * m, 4))
+        _check(self.L.bg_merge_join(build_sorted.ptr, nb, probe_sorted.ptr,
+                                    np_, ctypes.byref(matches), pbuf.ptr,
+                                    bbuf.ptr), "bg_merge_join(fill)")
+        return pbuf, bbuf, m
+
+    # ---- codecs ----
+    def _decompress(self, fn, job_cls, items):
+        """items: list of (src, src_len, dst, dst_cap), src/dst DeviceBuffers
+        or raw addresses. -> decompressed lengths (-1 = malformed)."""
+        arr = (job_cls * len(items))()
+        for i, (src, slen, dst, dcap) in enumerate(items):
+            arr[i] = job_cls(getattr(src, "ptr", src), getattr(dst, "ptr", dst),
+                             slen, dcap)
+        lens = np.zeros(len(items), dtype=np.int64)
+        _check(getattr(self.L, fn)(arr, len(items), lens.ctypes.data), fn)
+        return lens.tolist()
+
+    def snappy_decompress(self, pages):
+        """pages: list of (src DeviceBuffer, src_len, dst DeviceBuffer,
+        dst_cap). -> list of decompressed lengths (-1 = malformed)."""
+        return self._decompress("bg_snappy_decompress", BgSnappyPage, pages)
+
+    def lz4_decompress(self, frames):
+        """frames: list of (src DeviceBuffer, src_len, dst DeviceBuffer,
+        dst_cap) pointing at LZ4 frame magic. -> decompressed lengths."""
+        return self._decompress("bg_lz4_decompress", BgLz4Frame, frames)
+
+    def lz4_compress(self, src: DeviceBuffer, length: int):
+        """Device LZ4 -> (block sizes i64[nblocks], negative = stored raw;
+        slots DeviceBuffer)."""
+        nblocks = (length + BG_LZ4_BLOCK - 1) // BG_LZ4_BLOCK if length else 0
+        slots = self.alloc(max(nblocks * BG_LZ4_SLOT_STRIDE, 8))
+        sizes = np.zeros(max(nblocks, 1), dtype=np.int64)
+        nb = ctypes.c_int64()
+        _check(self.L.bg_lz4_compress(src.ptr, length, slots.ptr,
+                                      sizes.ctypes.data, ctypes.byref(nb)),
+               "bg_lz4_compress")
+        return sizes[:nblocks], slots
+
 
 class GpuHashJoin:
     """INNER equi-join (Int64 keys) — bg_hashjoin_* wrapper.
@@ -339,8 +661,7 @@ class GpuHashJoin:
     def __init__(self, ctx: GpuStageContext, build_keys: BgColumn, n_build: int):
         self.ctx = ctx
         self._handle = ctypes.c_void_p()
-        _check(ctx.L.bg_hashjoin_build(ctypes.byref(build_keys),
-                                       ctypes.c_int64(n_build),
+        _check(ctx.L.bg_hashjoin_build(ctypes.byref(build_keys), n_build,
                                        ctypes.byref(self._handle)),
                "bg_hashjoin_build")
 
@@ -350,15 +671,13 @@ class GpuHashJoin:
         matches = ctypes.c_int64()
         _check(ctx.L.bg_hashjoin_probe_count(self._handle,
                                              ctypes.byref(probe_keys),
-                                             ctypes.c_int64(n_probe),
-                                             ctypes.byref(matches)),
+                                             n_probe, ctypes.byref(matches)),
                "bg_hashjoin_probe_count")
         m = matches.value
         pbuf = ctx.alloc(max(4 * m, 4))
         bbuf = ctx.alloc(max(4 * m, 4))
         _check(ctx.L.bg_hashjoin_probe_fill(self._handle,
-                                            ctypes.byref(probe_keys),
-                                            ctypes.c_int64(n_probe),
+                                            ctypes.byref(probe_keys), n_probe,
                                             pbuf.ptr, bbuf.ptr),
                "bg_hashjoin_probe_fill")
         return pbuf, bbuf, m
@@ -367,357 +686,3 @@ class GpuHashJoin:
         if self._handle and self._handle.value:
             self.ctx.L.bg_hashjoin_free(self._handle)
             self._handle = ctypes.c_void_p()
-
-
-BG_AGG_OP_SUM_DEC128 = 0
-BG_AGG_OP_SUM_I64 = 1
-BG_AGG_OP_MIN_I64 = 2
-BG_AGG_OP_MAX_I64 = 3
-BG_AGG_OP_SUM_F64 = 4
-BG_AGG_OP_MIN_F64 = 5
-BG_AGG_OP_MAX_F64 = 6
-
-
-def decode_agg_value(op, raw16: bytes):
-    """Accumulator bytes -> python int/float per aggregate op."""
-    import struct as _st
-    if op in (BG_AGG_OP_SUM_DEC128, BG_AGG_OP_SUM_I64):
-        return int.from_bytes(raw16, "little", signed=True)
-    if op == BG_AGG_OP_SUM_F64:
-        return _st.unpack("<d", raw16[:8])[0]
-    enc = int.from_bytes(raw16[:8], "little")
-    if op in (BG_AGG_OP_MIN_F64, BG_AGG_OP_MAX_F64):
-        if op == BG_AGG_OP_MIN_F64:
-            enc = ~enc & 0xFFFFFFFFFFFFFFFF
-        bits = (~enc & 0xFFFFFFFFFFFFFFFF) if not (enc >> 63)             else enc ^ (1 << 63)
-        return _st.unpack("<d", _st.pack("<Q", bits))[0]
-    if op == BG_AGG_OP_MAX_I64:
-        v = enc ^ (1 << 63)
-    else:  # MIN_I64
-        v = (~enc & 0xFFFFFFFFFFFFFFFF) ^ (1 << 63)
-    return v - (1 << 64) if v >= 1 << 63 else v
-
-
-def _ctx_hashagg(self, key_cols, agg_cols, agg_ops, n, max_groups,
-                 mask: "DeviceBuffer" = None, want_nncnt: bool = False):
-    """General hash group-by. -> (first_row u32[g], acc i128 bytes
-    [g, naggs], counts i64[g]) as numpy arrays (downloaded); with
-    want_nncnt also the per-(group, agg) NON-NULL input counts i64[g, naggs]
-    (SQL: SUM/MIN/MAX of an all-NULL group is NULL — nncnt 0 marks it)."""
-    naggs = len(agg_cols)
-    first = self.alloc(max(4 * max_groups, 4))
-    acc = self.alloc(max(16 * max_groups * max(naggs, 1), 16))
-    counts = self.alloc(max(8 * max_groups, 8))
-    nncnt = self.alloc(max(8 * max_groups * max(naggs, 1), 8))         if want_nncnt else None
-    karr = (BgColumn * len(key_cols))(*key_cols)
-    aarr = (BgColumn * max(naggs, 1))(*(agg_cols or [BgColumn()]))
-    oarr = (ctypes.c_int32 * max(naggs, 1))(*(agg_ops or [0]))
-    ng = ctypes.c_int64()
-    # auto-grow on table-full (the scheduler's row estimates can be low,
-    # like the reference's AQE-fed group estimates)
-    attempt_groups = max_groups
-    for _ in range(8):
-        if want_nncnt:
-            rc = self.L.bg_hashagg2(karr, len(key_cols), aarr, oarr, naggs,
-                                    mask.ptr if mask else None,
-                                    ctypes.c_int64(n),
-                                    ctypes.c_int64(attempt_groups), first.ptr,
-                                    acc.ptr, counts.ptr, nncnt.ptr,
-                                    ctypes.byref(ng))
-        else:
-            rc = self.L.bg_hashagg(karr, len(key_cols), aarr, oarr, naggs,
-                                   mask.ptr if mask else None,
-                                   ctypes.c_int64(n),
-                                   ctypes.c_int64(attempt_groups), first.ptr,
-                                   acc.ptr, counts.ptr, ctypes.byref(ng))
-        if rc == 0:
-            break
-        err = load_library().bg_last_error().decode()
-        if "table full" not in err or attempt_groups >= n:
-            _check(rc, "bg_hashagg")
-        attempt_groups = min(max(attempt_groups * 8, 64), max(n, 64))
-        # output buffers must grow with the group capacity
-        first = self.alloc(max(4 * attempt_groups, 4))
-        acc = self.alloc(max(16 * attempt_groups * max(naggs, 1), 16))
-        counts = self.alloc(max(8 * attempt_groups, 8))
-        if want_nncnt:
-            nncnt = self.alloc(max(8 * attempt_groups * max(naggs, 1), 8))
-    else:
-        _check(rc, "bg_hashagg")
-    g = ng.value
-    ret = (first.download(np.uint32, g),
-           acc.download(np.uint8, 16 * g * naggs).reshape(g, naggs, 16)
-           if naggs else np.zeros((g, 0, 16), dtype=np.uint8),
-           counts.download(np.int64, g))
-    if want_nncnt:
-        nn = nncnt.download(np.int64, g * naggs).reshape(g, max(naggs, 1))             if naggs else np.zeros((g, 0), dtype=np.int64)
-        return ret + (nn,)
-    return ret
-
-
-GpuStageContext.hashagg = _ctx_hashagg
-
-
-BG_PROJ_MUL = 0
-BG_PROJ_ADD = 1
-BG_PROJ_SUB = 2
-BG_PROJ_RSUB_LIT = 3
-BG_PROJ_MUL_LIT = 4
-BG_PROJ_ADD_LIT = 5
-
-
-def _ctx_project_dec128(self, op, a: BgColumn, b: BgColumn, lit, n):
-    out = self.alloc(max(16 * n, 16))
-    lo, hi = _split_i128(lit)
-    _check(self.L.bg_project_dec128(op, ctypes.byref(a),
-                                    ctypes.byref(b) if b else None,
-                                    ctypes.c_int64(lo), ctypes.c_int64(hi),
-                                    ctypes.c_int64(n), out.ptr),
-           "bg_project_dec128")
-    return out
-
-
-GpuStageContext.project_dec128 = _ctx_project_dec128
-
-
-def _ctx_sort_rows(self, key_cols, descending, n):
-    """Stable multi-column ORDER BY -> row permutation DeviceBuffer."""
-    perm = self.alloc(max(4 * n, 4))
-    karr = (BgColumn * len(key_cols))(*key_cols)
-    darr = (ctypes.c_int32 * len(key_cols))(*[1 if d else 0
-                                              for d in descending])
-    _check(self.L.bg_sort_rows(karr, darr, len(key_cols),
-                               ctypes.c_int64(n), perm.ptr), "bg_sort_rows")
-    return perm
-
-
-GpuStageContext.sort_rows = _ctx_sort_rows
-
-
-def _ctx_merge_join(self, build_sorted: "DeviceBuffer", nb: int,
-                    probe_sorted: "DeviceBuffer", np_: int):
-    """Inner merge join of key-sorted i64 buffers -> (probe_pos, build_pos
-    DeviceBuffers into the sorted orders, n_matches)."""
-    matches = ctypes.c_int64()
-    _check(self.L.bg_merge_join(build_sorted.ptr, ctypes.c_int64(nb),
-                                probe_sorted.ptr, ctypes.c_int64(np_),
-                                ctypes.byref(matches), None, None),
-           "bg_merge_join(count)")
-    m = matches.value
-    pbuf = self.alloc(max(4 * m, 4))
-    bbuf = self.alloc(max(4 * m, 4))
-    _check(self.L.bg_merge_join(build_sorted.ptr, ctypes.c_int64(nb),
-                                probe_sorted.ptr, ctypes.c_int64(np_),
-                                ctypes.byref(matches), pbuf.ptr, bbuf.ptr),
-           "bg_merge_join(fill)")
-    return pbuf, bbuf, m
-
-
-GpuStageContext.merge_join = _ctx_merge_join
-
-
-class BgSnappyPage(ctypes.Structure):
-    _fields_ = [("d_src", ctypes.c_void_p), ("d_dst", ctypes.c_void_p),
-                ("src_len", ctypes.c_int64), ("dst_cap", ctypes.c_int64)]
-
-
-def _ctx_snappy_decompress(self, pages):
-    """pages: list of (src DeviceBuffer, src_len, dst DeviceBuffer,
-    dst_cap). -> list of decompressed lengths (-1 = malformed)."""
-    n = len(pages)
-    arr = (BgSnappyPage * n)()
-    for i, (src, slen, dst, dcap) in enumerate(pages):
-        arr[i] = BgSnappyPage(src.ptr, dst.ptr, slen, dcap)
-    lens = np.zeros(n, dtype=np.int64)
-    _check(self.L.bg_snappy_decompress(
-        arr, ctypes.c_int64(n),
-        lens.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
-        "bg_snappy_decompress")
-    return lens.tolist()
-
-
-GpuStageContext.snappy_decompress = _ctx_snappy_decompress
-
-
-class BgPageExtractJob(ctypes.Structure):
-    _fields_ = [("d_page", ctypes.c_void_p), ("d_out", ctypes.c_void_p),
-                ("page_len", ctypes.c_int64), ("nvals", ctypes.c_int64),
-                ("src_esz", ctypes.c_int64), ("has_def", ctypes.c_int32),
-                ("flba_reverse", ctypes.c_int32),
-                ("d_vidx", ctypes.c_void_p),
-                ("d_n_present", ctypes.c_void_p)]
-
-
-class BgDictIndicesJob(ctypes.Structure):
-    _fields_ = [("d_page", ctypes.c_void_p), ("d_out_idx", ctypes.c_void_p),
-                ("page_len", ctypes.c_int64), ("nvals", ctypes.c_int64),
-                ("has_def", ctypes.c_int32), ("_pad", ctypes.c_int32),
-                ("d_vidx", ctypes.c_void_p),
-                ("d_n_present", ctypes.c_void_p),
-                ("d_dense", ctypes.c_void_p)]
-
-
-class BgBaPageJob(ctypes.Structure):
-    _fields_ = [("d_page", ctypes.c_void_p),
-                ("d_lens_out", ctypes.c_void_p),
-                ("d_srcaddr_out", ctypes.c_void_p),
-                ("page_len", ctypes.c_int64), ("nvals", ctypes.c_int64),
-                ("has_def", ctypes.c_int32), ("_pad", ctypes.c_int32),
-                ("d_vidx", ctypes.c_void_p),
-                ("d_n_present", ctypes.c_void_p)]
-
-
-class BgDeltaBpJob(ctypes.Structure):
-    _fields_ = [("d_page", ctypes.c_void_p), ("d_out", ctypes.c_void_p),
-                ("page_len", ctypes.c_int64), ("nvals", ctypes.c_int64),
-                ("esz", ctypes.c_int64),
-                ("has_def", ctypes.c_int32), ("_pad", ctypes.c_int32),
-                ("d_vidx", ctypes.c_void_p),
-                ("d_n_present", ctypes.c_void_p)]
-
-
-class BgDeltaBaJob(ctypes.Structure):
-    _fields_ = [("d_page", ctypes.c_void_p),
-                ("d_lens_out", ctypes.c_void_p),
-                ("d_srcaddr_out", ctypes.c_void_p),
-                ("d_offs32", ctypes.c_void_p),
-                ("d_data_out", ctypes.c_void_p),
-                ("page_len", ctypes.c_int64), ("nvals", ctypes.c_int64),
-                ("has_def", ctypes.c_int32), ("enc", ctypes.c_int32),
-                ("d_vidx", ctypes.c_void_p),
-                ("d_n_present", ctypes.c_void_p)]
-
-
-class BgDefLevelsJob(ctypes.Structure):
-    _fields_ = [("d_page", ctypes.c_void_p), ("d_vidx", ctypes.c_void_p),
-                ("d_valid_out", ctypes.c_void_p),
-                ("page_len", ctypes.c_int64), ("nvals", ctypes.c_int64),
-                ("bit_off", ctypes.c_int64),
-                ("d_n_present", ctypes.c_void_p)]
-
-
-class BgListLevelsJob(ctypes.Structure):
-    _fields_ = [("d_page", ctypes.c_void_p), ("page_len", ctypes.c_int64),
-                ("nslots", ctypes.c_int64), ("max_def", ctypes.c_int32),
-                ("def_entry", ctypes.c_int32),
-                ("def_valid", ctypes.c_int32), ("_pad", ctypes.c_int32),
-                ("row_base", ctypes.c_int64),
-                ("entry_base", ctypes.c_int64),
-                ("d_counts", ctypes.c_void_p),
-                ("d_row_sizes", ctypes.c_void_p),
-                ("d_list_valid", ctypes.c_void_p),
-                ("d_elem_valid", ctypes.c_void_p),
-                ("d_vidx", ctypes.c_void_p)]
-
-
-def _ctx_gather_varlen(self, src_data: "DeviceBuffer", src_offsets: "DeviceBuffer",
-                       idx: "DeviceBuffer", m: int, max_bytes: int):
-    """Variable-length take -> (offsets buf i32[m+1], data buf, total)."""
-    out_offs = self.alloc(max(4 * (m + 1), 8))
-    out_data = self.alloc(max(max_bytes, 1))
-    total = ctypes.c_int64()
-    _check(self.L.bg_gather_varlen(src_data.ptr, src_offsets.ptr, idx.ptr,
-                                   ctypes.c_int64(m), out_offs.ptr,
-                                   out_data.ptr, ctypes.c_int64(max_bytes),
-                                   ctypes.byref(total)), "bg_gather_varlen")
-    return out_offs, out_data, total.value
-
-
-GpuStageContext.gather_varlen = _ctx_gather_varlen
-
-
-LZ4_FRAME_HEADER = bytes.fromhex("04224d184040c0")  # magic+FLG+BD+HC
-
-
-def _ctx_lz4_compress(self, src: "DeviceBuffer", length: int):
-    """Device LZ4 -> (list of (size, is_stored), slots DeviceBuffer)."""
-    nblocks = (length + 65536 - 1) // 65536 if length else 0
-    slots = self.alloc(max(nblocks * 65544, 8))
-    sizes = np.zeros(max(nblocks, 1), dtype=np.int64)
-    nb = ctypes.c_int64()
-    _check(self.L.bg_lz4_compress(src.ptr, ctypes.c_int64(length), slots.ptr,
-                                  sizes.ctypes.data_as(
-                                      ctypes.POINTER(ctypes.c_int64)),
-                                  ctypes.byref(nb)), "bg_lz4_compress")
-    return sizes[:nblocks], slots
-
-
-def lz4_frame_assemble(sizes, slot_bytes: bytes, length: int) -> bytes:
-    """Host glue: device block slots -> one LZ4 frame (constant header,
-    [u32 size] blocks — high bit = stored — end mark)."""
-    import struct
-    out = [LZ4_FRAME_HEADER]
-    for i, sz in enumerate(sizes):
-        base = i * 65544
-        blen = min(65536, length - i * 65536)
-        if sz < 0:  # stored raw
-            out.append(struct.pack("<I", blen | 0x80000000))
-            out.append(slot_bytes[base:base + blen])
-        else:
-            out.append(struct.pack("<I", int(sz)))
-            out.append(slot_bytes[base:base + int(sz)])
-    out.append(b"\x00\x00\x00\x00")
-    return b"".join(out)
-
-
-GpuStageContext.lz4_compress = _ctx_lz4_compress
-
-
-class BgPackJob(ctypes.Structure):
-    _fields_ = [("d_src", ctypes.c_void_p), ("d_dst", ctypes.c_void_p),
-                ("nbytes", ctypes.c_int64), ("size_word", ctypes.c_uint32),
-                ("_pad", ctypes.c_uint32)]
-
-
-class BgLz4BlockJob(ctypes.Structure):
-    _fields_ = [("d_src", ctypes.c_void_p), ("d_dst_slot", ctypes.c_void_p),
-                ("blen", ctypes.c_int32), ("_pad", ctypes.c_int32)]
-
-
-def _ctx_hash_repartition_fused(self, key_cols, payload_cols, n: int, k: int):
-    """Fused one-pass materialiser (k<=64, <=4 fixed-width payload cols):
-    same outputs/stable order as hash_repartition."""
-    idx = self.alloc(max(4 * n, 4))
-    offs = self.alloc(8 * (k + 1))
-    rank = self.alloc(max(4 * n, 4))
-    outs = []
-    optrs = (ctypes.c_void_p * len(payload_cols))()
-    for i, c in enumerate(payload_cols):
-        esz = _DT_SIZE[c.dtype]
-        b = self.alloc(max(esz * n, esz))
-        outs.append(b)
-        optrs[i] = b.ptr.value
-    karr = (BgColumn * len(key_cols))(*key_cols)
-    parr = (BgColumn * len(payload_cols))(*payload_cols)
-    _check(self.L.bg_hash_repartition_fused(
-        karr, len(key_cols), parr, len(payload_cols), ctypes.c_int64(n), k,
-        idx.ptr, offs.ptr, rank.ptr, optrs), "bg_hash_repartition_fused")
-    return idx, offs, outs
-
-
-GpuStageContext.hash_repartition_fused = _ctx_hash_repartition_fused
-
-
-class BgLz4Frame(ctypes.Structure):
-    _fields_ = [("d_src", ctypes.c_void_p), ("d_dst", ctypes.c_void_p),
-                ("src_len", ctypes.c_int64), ("dst_cap", ctypes.c_int64)]
-
-
-def _ctx_lz4_decompress(self, frames):
-    """frames: list of (src DeviceBuffer, src_len, dst DeviceBuffer,
-    dst_cap) pointing at LZ4 frame magic. -> decompressed lengths."""
-    n = len(frames)
-    arr = (BgLz4Frame * n)()
-    for i, (src, slen, dst, dcap) in enumerate(frames):
-        arr[i] = BgLz4Frame(src.ptr if hasattr(src, "ptr") else src,
-                            dst.ptr if hasattr(dst, "ptr") else dst,
-                            slen, dcap)
-    lens = np.zeros(n, dtype=np.int64)
-    _check(self.L.bg_lz4_decompress(
-        arr, ctypes.c_int64(n),
-        lens.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
-        "bg_lz4_decompress")
-    return lens.tolist()
-
-
-GpuStageContext.lz4_decompress = _ctx_lz4_decompress

@@ -23,6 +23,8 @@ parquet-format spec (PageHeader/DataPageHeader structs); parity is pinned
 against pyarrow's own reader in tests.
 """
 
+import ctypes
+
 import numpy as np
 import pyarrow as pa
 import pyarrow.parquet as pq
@@ -150,6 +152,30 @@ _PHYS_NP = {
 }
 
 
+def _snappy_pages(ctx, chunk, scratch, jobs):
+    """One batched bg_snappy_decompress of `jobs` = (file_off, csz,
+    scratch_off, usz) pages from the resident file buffer into their
+    scratch slots; raises on a page that does not decode to usz bytes."""
+    arr = (gpu.BgSnappyPage * len(jobs))()
+    for i, (poff, csz, soff, usz) in enumerate(jobs):
+        arr[i] = gpu.BgSnappyPage(chunk.at(poff), scratch.at(soff), csz, usz)
+    lens = np.zeros(len(jobs), dtype=np.int64)
+    gpu._check(ctx.L.bg_snappy_decompress(arr, len(jobs), lens.ctypes.data),
+               "bg_snappy_decompress")
+    for i, (_, _, _, usz) in enumerate(jobs):
+        if lens[i] != usz:
+            raise RuntimeError(f"snappy page {i} failed ({lens[i]})")
+
+
+def _nullable_ptrs(vidx, npres, slot, page):
+    """The (d_vidx, d_n_present) pair of a mode-2 job: the slot -> value-
+    index map from `slot` on and the page's present-count cell.  A required
+    column has neither (vidx is None): (None, None)."""
+    if vidx is None:
+        return None, None
+    return vidx.at(4 * slot), npres.at(8 * page)
+
+
 class GpuParquetColumnReader:
     """Decode one (row_group, column) chunk to a contiguous device buffer."""
 
@@ -200,7 +226,6 @@ class GpuParquetColumnReader:
         else:
             raise RuntimeError(f"physical type {phys} not GPU-decodable yet")
 
-        import ctypes
         chunk = self._file_buf  # page offsets below are absolute file offsets
         if self.pf.schema.column(col).max_repetition_level > 0:
             # nested column through the FLAT path would misread the page
@@ -272,9 +297,6 @@ class GpuParquetColumnReader:
                 pos = data_pos + csz
 
         scratch = ctx.alloc(max(scratch_total, 256))
-
-        def page_ptr(base, off):
-            return ctypes.c_void_p(base.ptr.value + off)
 
         ba = phys == "BYTE_ARRAY"
         if ba:
@@ -355,36 +377,21 @@ class GpuParquetColumnReader:
             for (kind, soff, foff, dlen) in v2_fixups:
                 if kind == "raw":  # uncompressed values copy (may be empty)
                     if dlen:
-                        gpu._check(ctx.L.bg_memcpy_dtod(
-                            ctypes.c_void_p(scratch.ptr.value + soff),
-                            ctypes.c_void_p(chunk.ptr.value + foff),
-                            ctypes.c_uint64(dlen)), "v2 values copy")
+                        gpu._check(ctx.L.bg_memcpy_dtod(scratch.at(soff),
+                                                        chunk.at(foff), dlen),
+                                   "v2 values copy")
                     continue
-                gpu._check(ctx.L.bg_memcpy_dtod(
-                    ctypes.c_void_p(scratch.ptr.value + soff),
-                    ctypes.c_void_p(pbuf.ptr.value + 4 * pi),
-                    ctypes.c_uint64(4)), "v2 dlen prefix")
+                gpu._check(ctx.L.bg_memcpy_dtod(scratch.at(soff),
+                                                pbuf.at(4 * pi), 4),
+                           "v2 dlen prefix")
                 pi += 1
                 if dlen:
-                    gpu._check(ctx.L.bg_memcpy_dtod(
-                        ctypes.c_void_p(scratch.ptr.value + soff + 4),
-                        ctypes.c_void_p(chunk.ptr.value + foff),
-                        ctypes.c_uint64(dlen)), "v2 def levels copy")
+                    gpu._check(ctx.L.bg_memcpy_dtod(scratch.at(soff + 4),
+                                                    chunk.at(foff), dlen),
+                               "v2 def levels copy")
 
         if codec == "SNAPPY":
-            arr = (gpu.BgSnappyPage * len(snappy_jobs))()
-            for i, (poff, csz, soff, usz) in enumerate(snappy_jobs):
-                arr[i] = gpu.BgSnappyPage(
-                    ctypes.c_void_p(chunk.ptr.value + poff),
-                    ctypes.c_void_p(scratch.ptr.value + soff), csz, usz)
-            lens = np.zeros(len(snappy_jobs), dtype=np.int64)
-            gpu._check(ctx.L.bg_snappy_decompress(
-                arr, ctypes.c_int64(len(snappy_jobs)),
-                lens.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
-                "bg_snappy_decompress")
-            for i, (_, _, _, usz) in enumerate(snappy_jobs):
-                if lens[i] != usz:
-                    raise RuntimeError(f"snappy page {i} failed ({lens[i]})")
+            _snappy_pages(ctx, chunk, scratch, snappy_jobs)
         elif codec in ("ZSTD", "GZIP"):
             if any(h[9] is not None for h in headers):
                 raise RuntimeError(
@@ -396,9 +403,8 @@ class GpuParquetColumnReader:
                 dec = pa_codec.decompress(self.raw[poff:poff + csz],
                                           decompressed_size=usz)
                 host[soff:soff + usz] = np.frombuffer(dec, dtype=np.uint8)
-            gpu._check(ctx.L.bg_memcpy_h2d(
-                scratch.ptr, host.ctypes.data_as(ctypes.c_void_p),
-                ctypes.c_uint64(scratch_total)), "bg_memcpy_h2d")
+            gpu._check(ctx.L.bg_memcpy_h2d(scratch.ptr, host.ctypes.data,
+                                           scratch_total), "bg_memcpy_h2d")
         else:
             # uncompressed: device-to-device copy page payloads into the
             # aligned scratch slots
@@ -406,10 +412,9 @@ class GpuParquetColumnReader:
                  v2) in headers:
                 if v2 is not None:
                     continue  # synthesized above
-                gpu._check(ctx.L.bg_memcpy_dtod(
-                    ctypes.c_void_p(scratch.ptr.value + soff),
-                    ctypes.c_void_p(chunk.ptr.value + poff),
-                    ctypes.c_uint64(csz)), "bg_memcpy_dtod")
+                gpu._check(ctx.L.bg_memcpy_dtod(scratch.at(soff),
+                                                chunk.at(poff), csz),
+                           "bg_memcpy_dtod")
 
         # OPTIONAL column (max_def=1): decode definition levels on device
         # into the column validity bitmap + per-slot value indices, then
@@ -427,84 +432,55 @@ class GpuParquetColumnReader:
             djobs = (gpu.BgDefLevelsJob * len(data_pages))()
             for i, (soff, usz, dst_off, nvals) in enumerate(data_pages):
                 djobs[i] = gpu.BgDefLevelsJob(
-                    page_ptr(scratch, soff).value,
-                    ctypes.c_void_p(vidx.ptr.value + 4 * dst_off).value,
-                    valid.ptr.value, usz, nvals, dst_off,
-                    ctypes.c_void_p(npres.ptr.value + 8 * i).value)
-            gpu._check(ctx.L.bg_def_levels_batch(
-                djobs, ctypes.c_int64(len(data_pages))),
-                "bg_def_levels_batch")
+                    scratch.at(soff), vidx.at(4 * dst_off), valid.ptr.value,
+                    usz, nvals, dst_off, npres.at(8 * i))
+            gpu._check(ctx.L.bg_def_levels_batch(djobs, len(data_pages)),
+                       "bg_def_levels_batch")
         if extracts and ba:
             jobs = (gpu.BgBaPageJob * len(extracts))()
             for i, (soff, usz, dst_off, nvals, pidx) in enumerate(extracts):
                 jobs[i] = gpu.BgBaPageJob(
-                    page_ptr(scratch, soff).value,
-                    ctypes.c_void_p(ba_lens.ptr.value + 8 * dst_off).value,
-                    ctypes.c_void_p(ba_srcaddr.ptr.value
-                                    + 8 * dst_off).value,
-                    usz, nvals, mode, 0,
-                    ctypes.c_void_p(vidx.ptr.value + 4 * dst_off).value
-                    if mode else None,
-                    ctypes.c_void_p(npres.ptr.value + 8 * pidx).value
-                    if mode else None)
-            gpu._check(ctx.L.bg_ba_extract_batch(
-                jobs, ctypes.c_int64(len(extracts))), "bg_ba_extract_batch")
+                    scratch.at(soff), ba_lens.at(8 * dst_off),
+                    ba_srcaddr.at(8 * dst_off), usz, nvals, mode, 0,
+                    *_nullable_ptrs(vidx, npres, dst_off, pidx))
+            gpu._check(ctx.L.bg_ba_extract_batch(jobs, len(extracts)),
+                       "bg_ba_extract_batch")
         elif extracts:
             jobs = (gpu.BgPageExtractJob * len(extracts))()
             for i, (soff, usz, dst_off, nvals, pidx) in enumerate(extracts):
                 jobs[i] = gpu.BgPageExtractJob(
-                    page_ptr(scratch, soff).value,
-                    ctypes.c_void_p(out.ptr.value + dst_off * dst_esz).value,
-                    usz, nvals, src_esz, mode, 1 if flba else 0,
-                    ctypes.c_void_p(vidx.ptr.value + 4 * dst_off).value
-                    if mode else None,
-                    ctypes.c_void_p(npres.ptr.value + 8 * pidx).value
-                    if mode else None)
-            gpu._check(ctx.L.bg_page_extract_batch(
-                jobs, ctypes.c_int64(len(extracts))), "bg_page_extract_batch")
+                    scratch.at(soff), out.at(dst_off * dst_esz), usz, nvals,
+                    src_esz, mode, 1 if flba else 0,
+                    *_nullable_ptrs(vidx, npres, dst_off, pidx))
+            gpu._check(ctx.L.bg_page_extract_batch(jobs, len(extracts)),
+                       "bg_page_extract_batch")
         if delta_ba:
             jobs7 = (gpu.BgDeltaBaJob * len(delta_ba))()
             for i, (soff, usz, dst_off, nvals, pidx, enc) in \
                     enumerate(delta_ba):
                 jobs7[i] = gpu.BgDeltaBaJob(
-                    page_ptr(scratch, soff).value,
-                    ctypes.c_void_p(ba_lens.ptr.value + 8 * dst_off).value,
-                    ctypes.c_void_p(ba_srcaddr.ptr.value
-                                    + 8 * dst_off).value,
-                    None, None, usz, nvals, mode, enc,
-                    ctypes.c_void_p(vidx.ptr.value + 4 * dst_off).value
-                    if mode else None,
-                    ctypes.c_void_p(npres.ptr.value + 8 * pidx).value
-                    if mode else None)
-            gpu._check(ctx.L.bg_delta_ba_batch(
-                jobs7, ctypes.c_int64(len(delta_ba)), 1),
-                "bg_delta_ba_batch(1)")
+                    scratch.at(soff), ba_lens.at(8 * dst_off),
+                    ba_srcaddr.at(8 * dst_off), None, None, usz, nvals, mode,
+                    enc, *_nullable_ptrs(vidx, npres, dst_off, pidx))
+            gpu._check(ctx.L.bg_delta_ba_batch(jobs7, len(delta_ba), 1),
+                       "bg_delta_ba_batch(1)")
         if bss:
             jobs9 = (gpu.BgPageExtractJob * len(bss))()
             for i, (soff, usz, dst_off, nvals, pidx) in enumerate(bss):
                 jobs9[i] = gpu.BgPageExtractJob(
-                    page_ptr(scratch, soff).value,
-                    ctypes.c_void_p(out.ptr.value + dst_off * dst_esz).value,
-                    usz, nvals, src_esz, mode, 0,
-                    ctypes.c_void_p(vidx.ptr.value + 4 * dst_off).value
-                    if mode else None,
-                    ctypes.c_void_p(npres.ptr.value + 8 * pidx).value
-                    if mode else None)
-            gpu._check(ctx.L.bg_bss_batch(
-                jobs9, ctypes.c_int64(len(bss))), "bg_bss_batch")
+                    scratch.at(soff), out.at(dst_off * dst_esz), usz, nvals,
+                    src_esz, mode, 0,
+                    *_nullable_ptrs(vidx, npres, dst_off, pidx))
+            gpu._check(ctx.L.bg_bss_batch(jobs9, len(bss)), "bg_bss_batch")
         if deltas:
             djobs2 = (gpu.BgDeltaBpJob * len(deltas))()
             for i, (soff, usz, dst_off, nvals, pidx) in enumerate(deltas):
                 djobs2[i] = gpu.BgDeltaBpJob(
-                    page_ptr(scratch, soff).value,
-                    ctypes.c_void_p(out.ptr.value + dst_off * dst_esz).value,
-                    usz, nvals, dst_esz, mode, 0,
-                    ctypes.c_void_p(vidx.ptr.value + 4 * dst_off).value
-                    if mode else None,
-                    ctypes.c_void_p(npres.ptr.value + 8 * pidx).value
-                    if mode else None)
-            gpu._check(ctx.L.bg_delta_bp_batch(
-                djobs2, ctypes.c_int64(len(deltas))), "bg_delta_bp_batch")
+                    scratch.at(soff), out.at(dst_off * dst_esz), usz, nvals,
+                    dst_esz, mode, 0,
+                    *_nullable_ptrs(vidx, npres, dst_off, pidx))
+            gpu._check(ctx.L.bg_delta_bp_batch(djobs2, len(deltas)),
+                       "bg_delta_bp_batch")
 
         all_dict_pages = [(rg, pg) for rg, d in dict_runs.items()
                           for pg in d["pages"]]
@@ -521,20 +497,19 @@ class GpuParquetColumnReader:
                     dl = ctx.alloc(max(8 * ndict, 8))
                     da = ctx.alloc(max(8 * ndict, 8))
                     j1 = (gpu.BgBaPageJob * 1)(gpu.BgBaPageJob(
-                        page_ptr(scratch, dsoff).value, dl.ptr.value,
-                        da.ptr.value, dusz, ndict, 0, 0, None, None))
-                    gpu._check(ctx.L.bg_ba_extract_batch(
-                        j1, ctypes.c_int64(1)), "bg_ba_extract(dict)")
+                        scratch.at(dsoff), dl.ptr.value, da.ptr.value, dusz,
+                        ndict, 0, 0, None, None))
+                    gpu._check(ctx.L.bg_ba_extract_batch(j1, 1),
+                               "bg_ba_extract(dict)")
                     doffs = ctx.alloc(max(4 * (ndict + 1), 8))
                     tot = ctypes.c_int64()
-                    gpu._check(ctx.L.bg_ba_materialize(
-                        dl.ptr, da.ptr, ctypes.c_int64(ndict), doffs.ptr,
-                        None, ctypes.c_int64(0), ctypes.byref(tot)),
-                        "bg_ba_materialize(dict size)")
+                    gpu._check(ctx.L.bg_ba_materialize(dl.ptr, da.ptr, ndict,
+                                                       doffs.ptr, None, 0,
+                                                       ctypes.byref(tot)),
+                               "bg_ba_materialize(dict size)")
                     ddata = ctx.alloc(max(tot.value, 1))
                     gpu._check(ctx.L.bg_ba_materialize(
-                        dl.ptr, da.ptr, ctypes.c_int64(ndict), doffs.ptr,
-                        ddata.ptr, ctypes.c_int64(tot.value),
+                        dl.ptr, da.ptr, ndict, doffs.ptr, ddata.ptr, tot.value,
                         ctypes.byref(tot)), "bg_ba_materialize(dict)")
                     dict_bufs[rg] = (doffs, ddata)
             else:
@@ -546,12 +521,11 @@ class GpuParquetColumnReader:
                     dbuf = ctx.alloc(max(ndict * dst_esz, dst_esz))
                     dict_bufs[rg] = dbuf
                     djobs.append(gpu.BgPageExtractJob(
-                        page_ptr(scratch, dsoff).value, dbuf.ptr.value, dusz,
-                        ndict, src_esz, 0, 1 if flba else 0))
+                        scratch.at(dsoff), dbuf.ptr.value, dusz, ndict,
+                        src_esz, 0, 1 if flba else 0))
                 jarr = (gpu.BgPageExtractJob * len(djobs))(*djobs)
-                gpu._check(ctx.L.bg_page_extract_batch(
-                    jarr, ctypes.c_int64(len(djobs))),
-                    "bg_page_extract(dicts)")
+                gpu._check(ctx.L.bg_page_extract_batch(jarr, len(djobs)),
+                           "bg_page_extract(dicts)")
             # ONE batched index expansion over every dict-coded page
             nidx_total = sum(pg[3] for (_, pg) in all_dict_pages)
             idx = ctx.alloc(max(4 * nidx_total, 4))
@@ -562,20 +536,13 @@ class GpuParquetColumnReader:
             for i, (rg, (soff, usz, dst_off, nvals, pidx)) in \
                     enumerate(all_dict_pages):
                 jobs[i] = gpu.BgDictIndicesJob(
-                    page_ptr(scratch, soff).value,
-                    ctypes.c_void_p(idx.ptr.value + 4 * run).value,
-                    usz, nvals, mode, 0,
-                    ctypes.c_void_p(vidx.ptr.value + 4 * dst_off).value
-                    if mode else None,
-                    ctypes.c_void_p(npres.ptr.value + 8 * pidx).value
-                    if mode else None,
-                    ctypes.c_void_p(dense.ptr.value + 4 * run).value
-                    if mode else None)
+                    scratch.at(soff), idx.at(4 * run), usz, nvals, mode, 0,
+                    *_nullable_ptrs(vidx, npres, dst_off, pidx),
+                    dense.at(4 * run) if mode else None)
                 gathers.append((rg, run, dst_off, nvals))
                 run += nvals
-            gpu._check(ctx.L.bg_dict_indices_batch(
-                jobs, ctypes.c_int64(len(all_dict_pages))),
-                "bg_dict_indices_batch")
+            gpu._check(ctx.L.bg_dict_indices_batch(jobs, len(all_dict_pages)),
+                       "bg_dict_indices_batch")
             # merge adjacent pages of one rg into single gathers
             merged = []
             for rg, ioff, dst_off, nvals in gathers:
@@ -588,56 +555,39 @@ class GpuParquetColumnReader:
                 if ba:
                     doffs, ddata = dict_bufs[rg]
                     gpu._check(ctx.L.bg_ba_from_dict(
-                        ctypes.c_void_p(idx.ptr.value + 4 * ioff), doffs.ptr,
-                        ddata.ptr,
-                        ctypes.c_void_p(vidx.ptr.value + 4 * dst_off)
-                        if mode else None,
-                        ctypes.c_int64(nvals),
-                        ctypes.c_void_p(ba_lens.ptr.value + 8 * dst_off),
-                        ctypes.c_void_p(ba_srcaddr.ptr.value
-                                        + 8 * dst_off)),
-                        "bg_ba_from_dict")
+                        idx.at(4 * ioff), doffs.ptr, ddata.ptr,
+                        vidx.at(4 * dst_off) if mode else None, nvals,
+                        ba_lens.at(8 * dst_off), ba_srcaddr.at(8 * dst_off)),
+                               "bg_ba_from_dict")
                 else:
-                    gpu._check(ctx.L.bg_gather(
-                        dict_bufs[rg].ptr, ctypes.c_int64(dst_esz),
-                        ctypes.c_void_p(idx.ptr.value + 4 * ioff),
-                        ctypes.c_int64(nvals),
-                        ctypes.c_void_p(out.ptr.value + dst_off * dst_esz)),
-                        "bg_gather(dict)")
+                    gpu._check(ctx.L.bg_gather(dict_bufs[rg].ptr, dst_esz,
+                                               idx.at(4 * ioff), nvals,
+                                               out.at(dst_off * dst_esz)),
+                               "bg_gather(dict)")
         if ba:
             offs32 = ctx.alloc(max(4 * (total_values + 1), 8))
             tot = ctypes.c_int64()
-            gpu._check(ctx.L.bg_ba_materialize(
-                ba_lens.ptr, ba_srcaddr.ptr, ctypes.c_int64(total_values),
-                offs32.ptr, None, ctypes.c_int64(0),
-                ctypes.byref(tot)), "bg_ba_materialize(size)")
+            gpu._check(ctx.L.bg_ba_materialize(ba_lens.ptr, ba_srcaddr.ptr,
+                                               total_values, offs32.ptr, None,
+                                               0, ctypes.byref(tot)),
+                       "bg_ba_materialize(size)")
             cap = tot.value
             data = ctx.alloc(max(cap, 1))
             gpu._check(ctx.L.bg_ba_materialize(
-                ba_lens.ptr, ba_srcaddr.ptr, ctypes.c_int64(total_values),
-                offs32.ptr, data.ptr, ctypes.c_int64(cap),
-                ctypes.byref(tot)), "bg_ba_materialize")
+                ba_lens.ptr, ba_srcaddr.ptr, total_values, offs32.ptr,
+                data.ptr, cap, ctypes.byref(tot)), "bg_ba_materialize")
             enc7 = [d for d in delta_ba if d[5] == 7]
             if enc7:
                 jobs8 = (gpu.BgDeltaBaJob * len(enc7))()
                 for i, (soff, usz, dst_off, nvals, pidx, enc) in \
                         enumerate(enc7):
                     jobs8[i] = gpu.BgDeltaBaJob(
-                        page_ptr(scratch, soff).value,
-                        ctypes.c_void_p(ba_lens.ptr.value
-                                        + 8 * dst_off).value,
-                        ctypes.c_void_p(ba_srcaddr.ptr.value
-                                        + 8 * dst_off).value,
-                        ctypes.c_void_p(offs32.ptr.value
-                                        + 4 * dst_off).value,
+                        scratch.at(soff), ba_lens.at(8 * dst_off),
+                        ba_srcaddr.at(8 * dst_off), offs32.at(4 * dst_off),
                         data.ptr.value, usz, nvals, mode, enc,
-                        ctypes.c_void_p(vidx.ptr.value + 4 * dst_off).value
-                        if mode else None,
-                        ctypes.c_void_p(npres.ptr.value + 8 * pidx).value
-                        if mode else None)
-                gpu._check(ctx.L.bg_delta_ba_batch(
-                    jobs8, ctypes.c_int64(len(enc7)), 2),
-                    "bg_delta_ba_batch(2)")
+                        *_nullable_ptrs(vidx, npres, dst_off, pidx))
+                gpu._check(ctx.L.bg_delta_ba_batch(jobs8, len(enc7), 2),
+                           "bg_delta_ba_batch(2)")
             ctx.synchronize()
             return ((offs32, data, tot.value), total_values, "BYTE_ARRAY",
                     valid)
@@ -660,7 +610,6 @@ class GpuParquetColumnReader:
                 elem_valid=DeviceBuffer u32 words,
                 list_valid=DeviceBuffer u32 words or None (required list),
                 row_sizes=DeviceBuffer i32[nrows])"""
-        import ctypes
         ctx = self.ctx
         if rgs is None:
             rgs = range(self.pf.metadata.num_row_groups)
@@ -738,24 +687,11 @@ class GpuParquetColumnReader:
             if codec == "SNAPPY":
                 snappy_jobs.append((poff, csz, soff, usz))
             else:
-                gpu._check(ctx.L.bg_memcpy_dtod(
-                    ctypes.c_void_p(scratch.ptr.value + soff),
-                    ctypes.c_void_p(chunk.ptr.value + poff),
-                    ctypes.c_uint64(csz)), "bg_memcpy_dtod")
+                gpu._check(ctx.L.bg_memcpy_dtod(scratch.at(soff),
+                                                chunk.at(poff), csz),
+                           "bg_memcpy_dtod")
         if snappy_jobs:
-            arr = (gpu.BgSnappyPage * len(snappy_jobs))()
-            for i, (poff, csz, soff, usz) in enumerate(snappy_jobs):
-                arr[i] = gpu.BgSnappyPage(
-                    ctypes.c_void_p(chunk.ptr.value + poff),
-                    ctypes.c_void_p(scratch.ptr.value + soff), csz, usz)
-            lens = np.zeros(len(snappy_jobs), dtype=np.int64)
-            gpu._check(ctx.L.bg_snappy_decompress(
-                arr, ctypes.c_int64(len(snappy_jobs)),
-                lens.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
-                "bg_snappy_decompress")
-            for i, (_, _, _, usz) in enumerate(snappy_jobs):
-                if lens[i] != usz:
-                    raise RuntimeError(f"snappy page {i} failed")
+            _snappy_pages(ctx, chunk, scratch, snappy_jobs)
 
         data_idx = [i for i, h in enumerate(headers) if h[3] > 0]
         npages = len(data_idx)
@@ -765,13 +701,10 @@ class GpuParquetColumnReader:
         for j, i in enumerate(data_idx):
             (_, _, usz, nslots, enc, _, rg) = headers[i]
             jobs[j] = gpu.BgListLevelsJob(
-                ctypes.c_void_p(scratch.ptr.value + scratch_offs[i]).value,
-                usz, nslots, max_def, def_entry, def_valid, 0, 0, 0,
-                ctypes.c_void_p(counts.ptr.value + 32 * j).value,
-                None, None, None, None)
-        gpu._check(ctx.L.bg_list_levels_batch(
-            jobs, ctypes.c_int64(npages), ctypes.c_int32(1)),
-            "bg_list_levels_batch(1)")
+                scratch.at(scratch_offs[i]), usz, nslots, max_def, def_entry,
+                def_valid, 0, 0, 0, counts.at(32 * j), None, None, None, None)
+        gpu._check(ctx.L.bg_list_levels_batch(jobs, npages, 1),
+                   "bg_list_levels_batch(1)")
         ctx.synchronize()
         cts = counts.download(np.int64, 4 * npages).reshape(npages, 4)
         rows_pp, ents_pp, pres_pp, rlen_pp = (cts[:, 0], cts[:, 1],
@@ -795,17 +728,13 @@ class GpuParquetColumnReader:
         for j, i in enumerate(data_idx):
             (_, _, usz, nslots, enc, _, rg) = headers[i]
             jobs[j] = gpu.BgListLevelsJob(
-                ctypes.c_void_p(scratch.ptr.value + scratch_offs[i]).value,
-                usz, nslots, max_def, def_entry, def_valid, 0,
-                int(row_bases[j]), int(ent_bases[j]), None,
+                scratch.at(scratch_offs[i]), usz, nslots, max_def, def_entry,
+                def_valid, 0, int(row_bases[j]), int(ent_bases[j]), None,
                 row_sizes.ptr.value,
                 (list_valid if list_valid is not None else all_valid).ptr.value,
-                elem_valid.ptr.value,
-                ctypes.c_void_p(vidx.ptr.value + 4 * int(ent_bases[j]))
-                .value)
-        gpu._check(ctx.L.bg_list_levels_batch(
-            jobs, ctypes.c_int64(npages), ctypes.c_int32(2)),
-            "bg_list_levels_batch(2)")
+                elem_valid.ptr.value, vidx.at(4 * int(ent_bases[j])))
+        gpu._check(ctx.L.bg_list_levels_batch(jobs, npages, 2),
+                   "bg_list_levels_batch(2)")
 
         # element values (entry space) — mode-2 extract/dict re-pointed
         # past [u32 rlen][rep]; BYTE_ARRAY elements via the same
@@ -828,28 +757,20 @@ class GpuParquetColumnReader:
             bjobs = (gpu.BgBaPageJob * len(plain))()
             for i, (soff, plen, ebase, ents, j, rg) in enumerate(plain):
                 bjobs[i] = gpu.BgBaPageJob(
-                    ctypes.c_void_p(scratch.ptr.value + soff).value,
-                    ctypes.c_void_p(ba_lens.ptr.value + 8 * ebase).value,
-                    ctypes.c_void_p(ba_srcaddr.ptr.value
-                                    + 8 * ebase).value,
-                    plen, ents, 2, 0,
-                    ctypes.c_void_p(vidx.ptr.value + 4 * ebase).value,
-                    ctypes.c_void_p(npres.ptr.value + 8 * j).value)
-            gpu._check(ctx.L.bg_ba_extract_batch(
-                bjobs, ctypes.c_int64(len(plain))),
-                "bg_ba_extract_batch(list)")
+                    scratch.at(soff), ba_lens.at(8 * ebase),
+                    ba_srcaddr.at(8 * ebase), plen, ents, 2, 0,
+                    *_nullable_ptrs(vidx, npres, ebase, j))
+            gpu._check(ctx.L.bg_ba_extract_batch(bjobs, len(plain)),
+                       "bg_ba_extract_batch(list)")
         elif plain:
             ejobs = (gpu.BgPageExtractJob * len(plain))()
             for i, (soff, plen, ebase, ents, j, rg) in enumerate(plain):
                 ejobs[i] = gpu.BgPageExtractJob(
-                    ctypes.c_void_p(scratch.ptr.value + soff).value,
-                    ctypes.c_void_p(out.ptr.value + ebase * esz).value,
-                    plen, ents, src_esz, 2, 1 if flba else 0,
-                    ctypes.c_void_p(vidx.ptr.value + 4 * ebase).value,
-                    ctypes.c_void_p(npres.ptr.value + 8 * j).value)
-            gpu._check(ctx.L.bg_page_extract_batch(
-                ejobs, ctypes.c_int64(len(plain))),
-                "bg_page_extract_batch(list)")
+                    scratch.at(soff), out.at(ebase * esz), plen, ents, src_esz,
+                    2, 1 if flba else 0,
+                    *_nullable_ptrs(vidx, npres, ebase, j))
+            gpu._check(ctx.L.bg_page_extract_batch(ejobs, len(plain)),
+                       "bg_page_extract_batch(list)")
         if dict_pages:
             dict_bufs = {}
             for i, h in enumerate(headers):
@@ -859,36 +780,28 @@ class GpuParquetColumnReader:
                         dl = ctx.alloc(max(8 * ndict, 8))
                         da = ctx.alloc(max(8 * ndict, 8))
                         j1 = (gpu.BgBaPageJob * 1)(gpu.BgBaPageJob(
-                            ctypes.c_void_p(scratch.ptr.value
-                                            + dsoff).value,
-                            dl.ptr.value, da.ptr.value, dusz, ndict,
-                            0, 0, None, None))
-                        gpu._check(ctx.L.bg_ba_extract_batch(
-                            j1, ctypes.c_int64(1)), "bg_ba_extract(ldict)")
+                            scratch.at(dsoff), dl.ptr.value, da.ptr.value,
+                            dusz, ndict, 0, 0, None, None))
+                        gpu._check(ctx.L.bg_ba_extract_batch(j1, 1),
+                                   "bg_ba_extract(ldict)")
                         doffs = ctx.alloc(max(4 * (ndict + 1), 8))
                         tot = ctypes.c_int64()
                         gpu._check(ctx.L.bg_ba_materialize(
-                            dl.ptr, da.ptr, ctypes.c_int64(ndict),
-                            doffs.ptr, None, ctypes.c_int64(0),
+                            dl.ptr, da.ptr, ndict, doffs.ptr, None, 0,
                             ctypes.byref(tot)), "bg_ba_materialize(lsize)")
                         ddata = ctx.alloc(max(tot.value, 1))
                         gpu._check(ctx.L.bg_ba_materialize(
-                            dl.ptr, da.ptr, ctypes.c_int64(ndict),
-                            doffs.ptr, ddata.ptr,
-                            ctypes.c_int64(tot.value),
-                            ctypes.byref(tot)), "bg_ba_materialize(ldict)")
+                            dl.ptr, da.ptr, ndict, doffs.ptr, ddata.ptr,
+                            tot.value, ctypes.byref(tot)),
+                                   "bg_ba_materialize(ldict)")
                         dict_bufs[h[6]] = (doffs, ddata)
                     else:
                         dbuf = ctx.alloc(max(h[5] * esz, esz))
-                        j1 = (gpu.BgPageExtractJob * 1)(
-                            gpu.BgPageExtractJob(
-                                ctypes.c_void_p(scratch.ptr.value
-                                                + scratch_offs[i]).value,
-                                dbuf.ptr.value, h[2], h[5], src_esz, 0,
-                                1 if flba else 0))
-                        gpu._check(ctx.L.bg_page_extract_batch(
-                            j1, ctypes.c_int64(1)),
-                            "bg_page_extract(ldict)")
+                        j1 = (gpu.BgPageExtractJob * 1)(gpu.BgPageExtractJob(
+                            scratch.at(scratch_offs[i]), dbuf.ptr.value, h[2],
+                            h[5], src_esz, 0, 1 if flba else 0))
+                        gpu._check(ctx.L.bg_page_extract_batch(j1, 1),
+                                   "bg_page_extract(ldict)")
                         dict_bufs[h[6]] = dbuf
             nidx = sum(p[3] for p in dict_pages)
             idx = ctx.alloc(max(4 * nidx, 4))
@@ -899,48 +812,36 @@ class GpuParquetColumnReader:
             for i, (soff, plen, ebase, ents, j, rg) in \
                     enumerate(dict_pages):
                 djobs[i] = gpu.BgDictIndicesJob(
-                    ctypes.c_void_p(scratch.ptr.value + soff).value,
-                    ctypes.c_void_p(idx.ptr.value + 4 * run).value,
-                    plen, ents, 2, 0,
-                    ctypes.c_void_p(vidx.ptr.value + 4 * ebase).value,
-                    ctypes.c_void_p(npres.ptr.value + 8 * j).value,
-                    ctypes.c_void_p(dense.ptr.value + 4 * run).value)
+                    scratch.at(soff), idx.at(4 * run), plen, ents, 2, 0,
+                    *_nullable_ptrs(vidx, npres, ebase, j), dense.at(4 * run))
                 gathers.append((rg, run, ebase, ents))
                 run += ents
-            gpu._check(ctx.L.bg_dict_indices_batch(
-                djobs, ctypes.c_int64(len(dict_pages))),
-                "bg_dict_indices_batch(list)")
+            gpu._check(ctx.L.bg_dict_indices_batch(djobs, len(dict_pages)),
+                       "bg_dict_indices_batch(list)")
             for rg, ioff, ebase, ents in gathers:
                 if ba:
                     doffs, ddata = dict_bufs[rg]
                     gpu._check(ctx.L.bg_ba_from_dict(
-                        ctypes.c_void_p(idx.ptr.value + 4 * ioff),
-                        doffs.ptr, ddata.ptr,
-                        ctypes.c_void_p(vidx.ptr.value + 4 * ebase),
-                        ctypes.c_int64(ents),
-                        ctypes.c_void_p(ba_lens.ptr.value + 8 * ebase),
-                        ctypes.c_void_p(ba_srcaddr.ptr.value
-                                        + 8 * ebase)),
-                        "bg_ba_from_dict(list)")
+                        idx.at(4 * ioff), doffs.ptr, ddata.ptr,
+                        vidx.at(4 * ebase), ents, ba_lens.at(8 * ebase),
+                        ba_srcaddr.at(8 * ebase)), "bg_ba_from_dict(list)")
                 else:
-                    gpu._check(ctx.L.bg_gather(
-                        dict_bufs[rg].ptr, ctypes.c_int64(esz),
-                        ctypes.c_void_p(idx.ptr.value + 4 * ioff),
-                        ctypes.c_int64(ents),
-                        ctypes.c_void_p(out.ptr.value + ebase * esz)),
-                        "bg_gather(ldict)")
+                    gpu._check(ctx.L.bg_gather(dict_bufs[rg].ptr, esz,
+                                               idx.at(4 * ioff), ents,
+                                               out.at(ebase * esz)),
+                               "bg_gather(ldict)")
         if ba:
             offs32 = ctx.alloc(max(4 * (n_entries + 1), 8))
             tot = ctypes.c_int64()
-            gpu._check(ctx.L.bg_ba_materialize(
-                ba_lens.ptr, ba_srcaddr.ptr, ctypes.c_int64(n_entries),
-                offs32.ptr, None, ctypes.c_int64(0),
-                ctypes.byref(tot)), "bg_ba_materialize(lsz)")
+            gpu._check(ctx.L.bg_ba_materialize(ba_lens.ptr, ba_srcaddr.ptr,
+                                               n_entries, offs32.ptr, None, 0,
+                                               ctypes.byref(tot)),
+                       "bg_ba_materialize(lsz)")
             data = ctx.alloc(max(tot.value, 1))
-            gpu._check(ctx.L.bg_ba_materialize(
-                ba_lens.ptr, ba_srcaddr.ptr, ctypes.c_int64(n_entries),
-                offs32.ptr, data.ptr, ctypes.c_int64(tot.value),
-                ctypes.byref(tot)), "bg_ba_materialize(list)")
+            gpu._check(ctx.L.bg_ba_materialize(ba_lens.ptr, ba_srcaddr.ptr,
+                                               n_entries, offs32.ptr, data.ptr,
+                                               tot.value, ctypes.byref(tot)),
+                       "bg_ba_materialize(list)")
             out = (offs32, data, tot.value)
         ctx.synchronize()
         sizes = row_sizes.download(np.int32, max(n_rows, 1))[:n_rows]

@@ -277,11 +277,7 @@ def read_partition_gpu(ctx, data_path, index_path, partition_id, schema):
     equivalent for a GPU-resident next stage).  Fixed-width columns, null-
     free batches.  Returns (n_rows, {col_idx: DeviceBuffer}) with columns
     concatenated across the partition's batches."""
-    import ctypes
-
     import numpy as np
-
-    from . import gpu as g
 
     offsets = read_index(index_path)
     lo, hi = offsets[partition_id], offsets[partition_id + 1]
@@ -307,9 +303,8 @@ def read_partition_gpu(ctx, data_path, index_path, partition_id, schema):
             if c is None:
                 continue
             foff, flen, usize = c
-            dst = ctypes.c_void_p(out[ci].ptr.value + row_cursor * esz[ci])
-            frames.append((ctypes.c_void_p(raw_buf.ptr.value + foff), flen,
-                           dst, usize))
+            frames.append((raw_buf.at(foff), flen,
+                           out[ci].at(row_cursor * esz[ci]), usize))
             expected.append(usize)
         row_cursor += n_rows
     if frames:

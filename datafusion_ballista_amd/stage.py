@@ -45,18 +45,7 @@ def schema_json(schema: pa.Schema) -> list:
     return [field_json(n, t) for n, t in zip(schema.names, schema.types)]
 
 
-def _lib():
-    L = gpu.load_library()
-    L.bg_execute_stage.argtypes = [ctypes.c_char_p,
-                                   ctypes.POINTER(ctypes.c_char_p)]
-    L.bg_stage_validate.argtypes = [ctypes.c_char_p,
-                                    ctypes.POINTER(ctypes.c_char_p)]
-    L.bg_stage_free.argtypes = [ctypes.c_char_p]
-    L.bg_debug_rb_message.argtypes = [
-        ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32,
-        ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, ctypes.c_int64,
-        ctypes.c_int32, ctypes.POINTER(ctypes.c_char_p)]
-    return L
+_lib = gpu.load_library  # signatures are declared there, once
 
 
 def validate(plan: dict) -> dict:
@@ -136,9 +125,8 @@ def register_table(ctx: "gpu.GpuStageContext", name: str, table: pa.Table):
     L = gpu.load_library()
     carr = (gpu.BgColumn * len(cols))(*cols)
     narr = (ctypes.c_char_p * len(names))(*[s.encode() for s in names])
-    gpu._check(L.bg_stage_register_table(name.encode(), carr, narr,
-                                         len(cols), ctypes.c_int64(n)),
-               "bg_stage_register_table")
+    gpu._check(L.bg_stage_register_table(name.encode(), carr, narr, len(cols),
+                                         n), "bg_stage_register_table")
     return keep
 
 

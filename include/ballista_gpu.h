@@ -366,13 +366,13 @@ int bg_merge_join(const int64_t* d_build_sorted, int64_t nb,
  * host array of {src, dst, src_len, dst_cap} with DEVICE src/dst pointers;
  * h_out_lens receives decompressed lengths (-1 = malformed page). */
 typedef struct {
-  const void* d_src;
-  void* d_dst;
+  const uint8_t* d_src;
+  uint8_t* d_dst;
   int64_t src_len;
   int64_t dst_cap;
 } bg_snappy_page;
-int bg_snappy_decompress(const void* h_pages /* bg_snappy_page[npages] */,
-                         int64_t npages, int64_t* h_out_lens);
+int bg_snappy_decompress(const bg_snappy_page* h_pages, int64_t npages,
+                         int64_t* h_out_lens);
 
 /* Parquet data-page extraction (PLAIN, no nulls): validates the def-level
  * block (optional columns) on device, copies the value bytes into the
@@ -392,8 +392,8 @@ int bg_dict_indices(const void* d_page, int64_t page_len, int64_t nvals,
 /* Batched forms: the whole column's page list in one launch (chunks hold
  * few pages; per-page host loops starve the GPU). */
 typedef struct {
-  const void* d_page;
-  void* d_out;
+  const uint8_t* d_page;
+  uint8_t* d_out;
   int64_t page_len;
   int64_t nvals;
   int64_t src_esz;
@@ -402,10 +402,10 @@ typedef struct {
   const uint32_t* d_vidx;      /* mode 2: slot -> value index, ~0u = NULL */
   const int64_t* d_n_present;  /* mode 2: values in this page */
 } bg_page_extract_job;
-int bg_page_extract_batch(const void* h_jobs, int64_t njobs);
+int bg_page_extract_batch(const bg_page_extract_job* h_jobs, int64_t njobs);
 
 typedef struct {
-  const void* d_page;
+  const uint8_t* d_page;
   uint32_t* d_out_idx;
   int64_t page_len;
   int64_t nvals;
@@ -415,7 +415,7 @@ typedef struct {
   const int64_t* d_n_present;  /* mode 2 */
   uint32_t* d_dense;           /* mode 2: scratch, >= n_present u32 */
 } bg_dict_indices_job;
-int bg_dict_indices_batch(const void* h_jobs, int64_t njobs);
+int bg_dict_indices_batch(const bg_dict_indices_job* h_jobs, int64_t njobs);
 
 /* OPTIONAL-column definition levels (max_def=1; the RLE/bit-packed hybrid
  * of the parquet spec, as decoded by the reference's parquet crate
@@ -425,7 +425,7 @@ int bg_dict_indices_batch(const void* h_jobs, int64_t njobs);
  * (~0u = NULL), and n_present.  Feed vidx/n_present to the mode-2
  * extract/dict jobs above. */
 typedef struct {
-  const void* d_page;    /* page start ([u32 dlen][levels][values...]) */
+  const uint8_t* d_page;    /* page start ([u32 dlen][levels][values...]) */
   uint32_t* d_vidx;      /* u32[nvals] slice for this page */
   uint32_t* d_valid_out; /* column validity bitmap (u32 words, zeroed) */
   int64_t page_len;
@@ -433,7 +433,7 @@ typedef struct {
   int64_t bit_off;       /* absolute bit position of this page's slot 0 */
   int64_t* d_n_present;
 } bg_def_levels_job;
-int bg_def_levels_batch(const void* h_jobs, int64_t njobs);
+int bg_def_levels_batch(const bg_def_levels_job* h_jobs, int64_t njobs);
 
 /* LIST columns (repetition levels, max_rep == 1; parquet-format.md
  * "Nested Encoding" / the reference's arrow-rs list reader).  A V1 page
@@ -444,7 +444,7 @@ int bg_def_levels_batch(const void* h_jobs, int64_t njobs);
  * offsets = their prefix sum), the list/element validity bitmaps and
  * the page-local value index per entry.  Rows must not span pages. */
 typedef struct {
-  const void* d_page;   /* [u32 rlen][rep][u32 dlen][def][values] */
+  const uint8_t* d_page;   /* [u32 rlen][rep][u32 dlen][def][values] */
   int64_t page_len;
   int64_t nslots;       /* level entries (page header num_values) */
   int32_t max_def;
@@ -459,7 +459,8 @@ typedef struct {
   uint32_t* d_elem_valid;
   uint32_t* d_vidx;     /* pass 2: PAGE-LOCAL slice */
 } bg_list_levels_job;
-int bg_list_levels_batch(const void* h_jobs, int64_t njobs, int32_t pass);
+int bg_list_levels_batch(const bg_list_levels_job* h_jobs, int64_t njobs,
+                         int32_t pass);
 
 /* BYTE_ARRAY (Utf8/Binary) PLAIN pages (parquet spec PLAIN: [u32 len]
  * [bytes] per value; the reference's decoding.rs PlainDecoder):
@@ -469,7 +470,7 @@ int bg_list_levels_batch(const void* h_jobs, int64_t njobs, int32_t pass);
  * coded string pages bridge with bg_ba_from_dict (lengths/addresses from
  * the PLAIN-decoded dictionary through the expanded indices). */
 typedef struct {
-  const void* d_page;
+  const uint8_t* d_page;
   int64_t* d_lens_out;     /* i64[nvals] slice */
   int64_t* d_srcaddr_out;  /* i64[nvals] slice */
   int64_t page_len;
@@ -479,7 +480,7 @@ typedef struct {
   const uint32_t* d_vidx;
   const int64_t* d_n_present;
 } bg_ba_page_job;
-int bg_ba_extract_batch(const void* h_jobs, int64_t njobs);
+int bg_ba_extract_batch(const bg_ba_page_job* h_jobs, int64_t njobs);
 int bg_ba_from_dict(const uint32_t* d_idx, const int32_t* d_doffs,
                     const void* d_ddata, const uint32_t* d_vidx, int64_t n,
                     int64_t* d_lens_out, int64_t* d_srcaddr_out);
@@ -493,8 +494,8 @@ int bg_ba_materialize(const int64_t* d_lens, const int64_t* d_srcaddr,
  * page (the prefix chain is sequential), pages concurrent across waves;
  * nullable slots scatter through the def-level vidx map. */
 typedef struct {
-  const void* d_page;
-  void* d_out;           /* i32/i64 column slice */
+  const uint8_t* d_page;
+  uint8_t* d_out;        /* i32/i64 column slice */
   int64_t page_len;
   int64_t nvals;
   int64_t esz;           /* 4 or 8 */
@@ -503,7 +504,7 @@ typedef struct {
   const uint32_t* d_vidx;
   const int64_t* d_n_present;
 } bg_delta_bp_job;
-int bg_delta_bp_batch(const void* h_jobs, int64_t njobs);
+int bg_delta_bp_batch(const bg_delta_bp_job* h_jobs, int64_t njobs);
 
 /* DELTA_LENGTH_BYTE_ARRAY (6) / DELTA_BYTE_ARRAY (7) string pages — the
  * reference's parquet-rs V2 writer defaults for BYTE_ARRAY (Encodings.md;
@@ -512,7 +513,7 @@ int bg_delta_bp_batch(const void* h_jobs, int64_t njobs);
  * after bg_ba_materialize lays out the column, pass 2 (enc 7 only)
  * rebuilds each string from its predecessor's prefix + its suffix. */
 typedef struct {
-  const void* d_page;
+  const uint8_t* d_page;
   int64_t* d_lens_out;
   int64_t* d_srcaddr_out;
   const int32_t* d_offs32;  /* pass 2 */
@@ -524,12 +525,13 @@ typedef struct {
   const uint32_t* d_vidx;
   const int64_t* d_n_present;
 } bg_delta_ba_job;
-int bg_delta_ba_batch(const void* h_jobs, int64_t njobs, int32_t pass);
+int bg_delta_ba_batch(const bg_delta_ba_job* h_jobs, int64_t njobs,
+                      int32_t pass);
 
 /* BYTE_STREAM_SPLIT (encoding 9, fixed-width): parallel byte transpose
  * of the k per-byte streams back into values (bg_page_extract_job fields;
  * flba_reverse unused). */
-int bg_bss_batch(const void* h_jobs, int64_t njobs);
+int bg_bss_batch(const bg_page_extract_job* h_jobs, int64_t njobs);
 
 /* Device LZ4 block compression (the GPU shuffle codec's compress half,
  * SURVEY.md §8f row 3): 64 KiB blocks, one wave per block.  d_out_slots
@@ -543,33 +545,33 @@ int bg_lz4_compress(const void* d_src, int64_t len, void* d_out_slots,
                     int64_t* h_block_sizes, int64_t* out_nblocks);
 /* flat batched compression over many buffers' blocks in one launch */
 typedef struct {
-  const void* d_src;
-  void* d_dst_slot;
+  const uint8_t* d_src;
+  uint8_t* d_dst_slot;
   int32_t blen;
   int32_t _pad;
 } bg_lz4_block_job;
-int bg_lz4_compress_flat(const void* h_jobs, int64_t njobs,
+int bg_lz4_compress_flat(const bg_lz4_block_job* h_jobs, int64_t njobs,
                          int64_t* h_block_sizes);
 /* LZ4-frame DECODE on device (shuffle-read ingest; mirror of the
  * compressor).  h_frames entries point at frame magic; h_out_lens[i] =
  * decompressed bytes or -1 on malformed input. */
 typedef struct {
-  const void* d_src;
-  void* d_dst;
+  const uint8_t* d_src;
+  uint8_t* d_dst;
   int64_t src_len;
   int64_t dst_cap;
 } bg_lz4_frame;
-int bg_lz4_decompress(const void* h_frames, int64_t nframes,
+int bg_lz4_decompress(const bg_lz4_frame* h_frames, int64_t nframes,
                       int64_t* h_out_lens);
 /* assemble [u32 size][block] sequences on device at precomputed offsets */
 typedef struct {
-  const void* d_src;
-  void* d_dst;        /* at the 4-byte size word */
+  const uint8_t* d_src;
+  uint8_t* d_dst;     /* at the 4-byte size word */
   int64_t nbytes;
   uint32_t size_word; /* high bit = stored block */
   uint32_t _pad;
 } bg_pack_job;
-int bg_pack_blocks(const void* h_jobs, int64_t njobs);
+int bg_pack_blocks(const bg_pack_job* h_jobs, int64_t njobs);
 
 /* Fused repartition materialiser (k <= 64, <= 4 fixed-width payload
  * columns): one pass re-hashes keys, ranks rows per partition with
