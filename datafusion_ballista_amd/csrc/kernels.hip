@@ -812,9 +812,9 @@ __global__ void k_mask_scatter(const u64* words, int64_t nwords, int64_t n,
   }
 }
 
-extern "C" int bg_mask_to_indices(const uint8_t* d_mask, int64_t n,
-                                  uint32_t* d_indices, int64_t* out_count) {
-  REQUIRE_INIT();
+// d_indices == nullptr: count only (the scatter pass is skipped)
+static int mask_to_indices(const uint8_t* d_mask, int64_t n,
+                           uint32_t* d_indices, int64_t* out_count) {
   const int64_t nwords = (n + 63) / 64;
   const int64_t nchunks = (nwords + MC_WORDS_PER_WAVE - 1) / MC_WORDS_PER_WAVE;
   DevBuf<u64> d_counts;
@@ -831,13 +831,20 @@ extern "C" int bg_mask_to_indices(const uint8_t* d_mask, int64_t n,
     int rc = scan_exclusive_i64(d_counts, nchunks, d_offs, d_total);
     if (rc != BG_OK) return rc;
   }
-  hipLaunchKernelGGL(k_mask_scatter, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                     reinterpret_cast<const u64*>(d_mask), nwords, n, d_offs,
-                     nchunks, d_indices);
+  if (d_indices)
+    hipLaunchKernelGGL(k_mask_scatter, dim3(blocks), dim3(BG_BLOCK), 0, 0,
+                       reinterpret_cast<const u64*>(d_mask), nwords, n, d_offs,
+                       nchunks, d_indices);
   i64 total = 0;
   HIP_TRY(hipMemcpy(&total, d_total, sizeof(i64), hipMemcpyDeviceToHost));
   *out_count = total;
   return BG_OK;
+}
+
+extern "C" int bg_mask_to_indices(const uint8_t* d_mask, int64_t n,
+                                  uint32_t* d_indices, int64_t* out_count) {
+  REQUIRE_INIT();
+  return mask_to_indices(d_mask, n, d_indices, out_count);
 }
 
 // ---------------------------------------------------------------------------
@@ -6745,6 +6752,81 @@ __global__ void k_join_fill2(KeyArgs bkeys, KeyArgs pkeys, int64_t n_probe,
   }
 }
 
+// Build-side-preserving types (DataFusion's LeftSemi/LeftAnti/Left/Full,
+// build = its left input): one visited bit per build row, Arrow LSB order,
+// set by every probe row that matches it.  The plain load in front of the
+// atomic is only a hint (most marks are repeats: ~4 lineitems per order);
+// bits are set-only after a zeroing memset, so a stale 0 costs one
+// redundant atomicOr and a stale 1 cannot occur.  Readers are later
+// kernels on the same stream; nothing reads the bitmap inside a launch.
+__device__ __forceinline__ void mark_visited(uint32_t* words, int64_t row) {
+  uint32_t* w = &words[row >> 5];
+  const uint32_t bit = 1u << (row & 31);
+  if (!(*w & bit)) atomicOr(w, bit);  // result unused: no-return form
+}
+
+// k_join_count2's chain walk, run to the chain's end: every build row
+// with an equal key is marked, nothing is emitted
+__global__ void k_join_mark2(KeyArgs bkeys, KeyArgs pkeys, int64_t n_probe,
+                             const int* head, const ulong2* nodes, u64 mask,
+                             uint32_t* visited) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < n_probe; i += (int64_t)gridDim.x * blockDim.x) {
+    if (row_has_null_key(pkeys, i)) continue;
+    const u64 h = hash_keys_row(pkeys, i);
+    int64_t cur = head[h & mask];
+    while (cur >= 0) {
+      const ulong2 node = nodes[cur];
+      if (node.x == h && keys_equal_cross(bkeys, cur, pkeys, i))
+        mark_visited(visited, cur);
+      cur = (int64_t)node.y;
+    }
+  }
+}
+
+// k_join_fill2 for BG_JOIN_OUTER_BUILD (pairs as INNER) and
+// BG_JOIN_OUTER_FULL (pairs as OUTER_PROBE), marking each matched build
+// row.  A kernel of its own, so k_join_fill2 stays as it was.
+__global__ void k_join_fill_mark2(KeyArgs bkeys, KeyArgs pkeys,
+                                  int64_t n_probe, const int* head,
+                                  const ulong2* nodes, u64 mask,
+                                  int32_t keep_unmatched_probe,
+                                  const i64* offsets, uint32_t* out_probe,
+                                  uint32_t* out_build, uint32_t* visited) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < n_probe; i += (int64_t)gridDim.x * blockDim.x) {
+    i64 w = offsets[i];
+    bool matched = false;
+    if (!row_has_null_key(pkeys, i)) {
+      const u64 h = hash_keys_row(pkeys, i);
+      int64_t cur = head[h & mask];
+      while (cur >= 0) {
+        const ulong2 node = nodes[cur];
+        if (node.x == h && keys_equal_cross(bkeys, cur, pkeys, i)) {
+          matched = true;
+          out_probe[w] = (uint32_t)i;
+          out_build[w] = (uint32_t)cur;
+          ++w;
+          mark_visited(visited, cur);
+        }
+        cur = (int64_t)node.y;
+      }
+    }
+    if (!matched && keep_unmatched_probe) {
+      out_probe[w] = (uint32_t)i;
+      out_build[w] = BG_JOIN_NULL_IDX;
+    }
+  }
+}
+
+// ~visited (or all ones where nothing was ever marked) as a mask for the
+// stable compaction, which trims the bits at or beyond n itself
+__global__ void k_bitmap_not_u64(const u64* in, int64_t nwords, u64* out) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwords;
+       i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = in ? ~in[i] : ~0ull;
+}
+
 static int keyargs_from_cols(const bg_column* cols, int32_t nkeys,
                              KeyArgs* out) {
   if (nkeys <= 0 || nkeys > BG_MAX_KEYS) return BG_ERR_INVALID;
@@ -6779,7 +6861,44 @@ struct BgJoinTable2 {
   i64* probe_offsets = nullptr;
   int64_t probe_n = 0;
   int32_t probe_jt = -1;
+  // one visited bit per build row, ((n_build+63)/64)*8 + 8 bytes; allocated
+  // and zeroed by the first marking call, accumulated until free2
+  uint32_t* visited = nullptr;
 };
+
+static inline uint64_t join_visited_bytes(int64_t n_build) {
+  return (uint64_t)((n_build + 63) / 64) * 8 + 8;
+}
+
+// lazily allocate + zero the visited bitmap (stream-ordered memset: every
+// marking kernel is launched on the same null stream after it)
+static int join_ensure_visited(BgJoinTable2* t) {
+  if (t->visited) return BG_OK;
+  DevBuf<uint8_t> v;
+  HIP_TRY(v.alloc((int64_t)join_visited_bytes(t->n_build)));
+  HIP_TRY(hipMemsetAsync(v, 0, join_visited_bytes(t->n_build), 0));
+  t->visited = reinterpret_cast<uint32_t*>(v.detach());
+  return BG_OK;
+}
+
+// probe keys checked against the handle's build keys
+static int join_probe_keys(const BgJoinTable2* t, const bg_column* keys,
+                           int32_t nkeys, KeyArgs* pk) {
+  if (keyargs_from_cols(keys, nkeys, pk) != BG_OK || nkeys != t->nkeys)
+    return set_err(BG_ERR_UNSUPPORTED, "probe key dtype/count mismatch");
+  for (int c = 0; c < nkeys; ++c)
+    if (pk->k[c].dtype != t->bkeys.k[c].dtype)
+      return set_err(BG_ERR_INVALID, "probe/build key dtypes differ");
+  return BG_OK;
+}
+
+// SEMI_BUILD / ANTI_BUILD emit build rows, never pairs
+static int join_refuse_pairless(int32_t jt) {
+  if (jt != BG_JOIN_SEMI_BUILD && jt != BG_JOIN_ANTI_BUILD) return BG_OK;
+  return set_err(BG_ERR_INVALID,
+                 "SEMI_BUILD/ANTI_BUILD emit no pairs: call "
+                 "bg_hashjoin_probe_mark2, then bg_hashjoin_build_rows2");
+}
 
 extern "C" int bg_hashjoin_build2(const bg_column* keys, int32_t nkeys,
                                   int64_t n, void** out_handle) {
@@ -6816,11 +6935,15 @@ extern "C" int bg_hashjoin_probe_count2(void* handle, const bg_column* keys,
   REQUIRE_INIT();
   BgJoinTable2* t = (BgJoinTable2*)handle;
   KeyArgs pk;
-  if (keyargs_from_cols(keys, nkeys, &pk) != BG_OK || nkeys != t->nkeys)
-    return set_err(BG_ERR_UNSUPPORTED, "probe key dtype/count mismatch");
-  for (int c = 0; c < nkeys; ++c)
-    if (pk.k[c].dtype != t->bkeys.k[c].dtype)
-      return set_err(BG_ERR_INVALID, "probe/build key dtypes differ");
+  int krc = join_probe_keys(t, keys, nkeys, &pk);
+  if (krc != BG_OK) return krc;
+  if ((krc = join_refuse_pairless(join_type)) != BG_OK) return krc;
+  // the marking types count pairs exactly as the type they extend
+  const int32_t count_jt = join_type == BG_JOIN_OUTER_BUILD
+                               ? BG_JOIN_INNER
+                               : join_type == BG_JOIN_OUTER_FULL
+                                     ? BG_JOIN_OUTER_PROBE
+                                     : join_type;
   if (t->probe_offsets) {
     (void)pool_release(t->probe_offsets);
     t->probe_offsets = nullptr;
@@ -6833,7 +6956,7 @@ extern "C" int bg_hashjoin_probe_count2(void* handle, const bg_column* keys,
   HIP_TRY(d_total.alloc(1));
   int blocks = grid_for(n);
   hipLaunchKernelGGL(k_join_count2, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                     t->bkeys, pk, n, t->head, t->nodes, t->mask, join_type,
+                     t->bkeys, pk, n, t->head, t->nodes, t->mask, count_jt,
                      d_counts);
   HIP_TRY(hipGetLastError());
   int rc = scan_exclusive_u32(d_counts, n, d_offs, d_total);
@@ -6857,10 +6980,22 @@ extern "C" int bg_hashjoin_probe_fill2(void* handle, const bg_column* keys,
   KeyArgs pk;
   if (keyargs_from_cols(keys, nkeys, &pk) != BG_OK)
     return set_err(BG_ERR_UNSUPPORTED, "probe key dtype/count mismatch");
+  if (int rrc = join_refuse_pairless(join_type)) return rrc;
   if (!t->probe_offsets || t->probe_n != n || t->probe_jt != join_type)
     return set_err(BG_ERR_INVALID,
                    "call bg_hashjoin_probe_count2 first (same join_type)");
   int blocks = grid_for(n);
+  if (join_type == BG_JOIN_OUTER_BUILD || join_type == BG_JOIN_OUTER_FULL) {
+    int rc = join_ensure_visited(t);
+    if (rc != BG_OK) return rc;
+    hipLaunchKernelGGL(k_join_fill_mark2, dim3(blocks), dim3(BG_BLOCK), 0, 0,
+                       t->bkeys, pk, n, t->head, t->nodes, t->mask,
+                       join_type == BG_JOIN_OUTER_FULL ? 1 : 0,
+                       t->probe_offsets, d_out_probe, d_out_build,
+                       t->visited);
+    HIP_TRY(hipGetLastError());
+    return BG_OK;
+  }
   hipLaunchKernelGGL(k_join_fill2, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      t->bkeys, pk, n, t->head, t->nodes, t->mask, join_type,
                      t->probe_offsets, d_out_probe, d_out_build);
@@ -6875,8 +7010,54 @@ extern "C" int bg_hashjoin_free2(void* handle) {
   (void)pool_release(t->nodes);
   (void)pool_release(t->head);
   if (t->probe_offsets) (void)pool_release(t->probe_offsets);
+  if (t->visited) (void)pool_release(t->visited);
   delete t;
   return BG_OK;
+}
+
+extern "C" int bg_hashjoin_probe_mark2(void* handle, const bg_column* keys,
+                                       int32_t nkeys, int64_t n) {
+  REQUIRE_INIT();
+  BgJoinTable2* t = (BgJoinTable2*)handle;
+  if (!t) return set_err(BG_ERR_INVALID, "null join handle");
+  KeyArgs pk;
+  int rc = join_probe_keys(t, keys, nkeys, &pk);
+  if (rc != BG_OK) return rc;
+  rc = join_ensure_visited(t);
+  if (rc != BG_OK) return rc;
+  if (n <= 0) return BG_OK;
+  int blocks = grid_for(n);
+  hipLaunchKernelGGL(k_join_mark2, dim3(blocks), dim3(BG_BLOCK), 0, 0,
+                     t->bkeys, pk, n, t->head, t->nodes, t->mask, t->visited);
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+extern "C" int bg_hashjoin_build_rows2(void* handle, int32_t matched,
+                                       int64_t* out_count,
+                                       uint32_t* d_out_build) {
+  REQUIRE_INIT();
+  BgJoinTable2* t = (BgJoinTable2*)handle;
+  if (!t || !out_count)
+    return set_err(BG_ERR_INVALID, "null join handle / out_count");
+  if (matched != 0 && matched != 1)
+    return set_err(BG_ERR_INVALID, "matched must be 0 or 1");
+  *out_count = 0;
+  // nothing marked yet: no build row is matched
+  if (t->n_build == 0 || (matched && !t->visited)) return BG_OK;
+  if (matched)
+    return mask_to_indices(reinterpret_cast<const uint8_t*>(t->visited),
+                           t->n_build, d_out_build, out_count);
+  const int64_t nwords = (t->n_build + 63) / 64;
+  DevBuf<u64> inv;
+  HIP_TRY(inv.alloc(nwords));
+  hipLaunchKernelGGL(k_bitmap_not_u64, dim3(grid_for(nwords)),
+                     dim3(BG_BLOCK), 0, 0,
+                     reinterpret_cast<const u64*>(t->visited), nwords,
+                     inv.get());
+  HIP_TRY(hipGetLastError());
+  return mask_to_indices(reinterpret_cast<const uint8_t*>(inv.get()),
+                         t->n_build, d_out_build, out_count);
 }
 
 // sentinel handling for probe-outer joins: split an index vector carrying

@@ -281,6 +281,29 @@ static Col slice_col(const Col& c, int64_t start, int64_t len) {
   return s;
 }
 
+// m all-NULL rows of `like`'s dtype, precision and scale (Utf8: zero
+// offsets, 0 data bytes): the NULL-extended side of an outer join's
+// unmatched rows.
+static Col null_col(const Col& like, int64_t m) {
+  Col out;
+  out.dtype = like.dtype;
+  out.precision = like.precision;
+  out.scale = like.scale;
+  if (like.dtype == BG_DT_UTF8) {
+    out.offsets = dalloc((uint64_t)(m + 1) * 4);
+    chk(bg_memset(out.offsets->p, 0, out.offsets->bytes), "bg_memset");
+    out.data = dalloc(1);
+    out.data_bytes = 0;
+  } else {
+    const int64_t esz = dt_size(like.dtype);
+    out.data = dalloc((uint64_t)(m > 0 ? m : 1) * (uint64_t)esz);
+    chk(bg_memset(out.data->p, 0, out.data->bytes), "bg_memset");
+  }
+  out.validity = dalloc((uint64_t)((m + 63) / 64) * 8 + 8);
+  chk(bg_memset(out.validity->p, 0, out.validity->bytes), "bg_memset");
+  return out;
+}
+
 // Concatenate row-aligned column pieces (the chunked-probe merge).
 static Col concat_cols(const std::vector<Col>& pieces,
                        const std::vector<int64_t>& lens) {
@@ -1391,6 +1414,15 @@ static Table exec_project(const Value& node, Metrics& m) {
   return out;
 }
 
+// semi_build / anti_build emit build rows only (execution and
+// bg_stage_validate both check)
+static void require_build_side(const std::string& jt, const Value& o) {
+  if (o.get_str("side") != "build")
+    throw StageError(BG_ERR_INVALID,
+                     "hash_join: " + jt + " emits build rows only; output '" +
+                         o.get_str("col") + "' is not side 'build'");
+}
+
 static Table exec_join(const Value& node, Metrics& m) {
   Table build = exec_plan(node.at("build"), m);
   Table probe = exec_plan(node.at("probe"), m);
@@ -1404,6 +1436,11 @@ static Table exec_join(const Value& node, Metrics& m) {
   else if (jt == "semi") join_type = BG_JOIN_SEMI;
   else if (jt == "anti") join_type = BG_JOIN_ANTI;
   else if (jt == "left") join_type = BG_JOIN_OUTER_PROBE;  // probe preserved
+  // build preserved (DataFusion LeftSemi / LeftAnti / Left / Full)
+  else if (jt == "semi_build") join_type = BG_JOIN_SEMI_BUILD;
+  else if (jt == "anti_build") join_type = BG_JOIN_ANTI_BUILD;
+  else if (jt == "outer_build") join_type = BG_JOIN_OUTER_BUILD;
+  else if (jt == "full") join_type = BG_JOIN_OUTER_FULL;
   else
     throw StageError(BG_ERR_UNSUPPORTED, "hash_join: join_type " + jt);
 
@@ -1444,22 +1481,62 @@ static Table exec_join(const Value& node, Metrics& m) {
   if (chunk <= 0 || chunk >= probe.n) chunk = probe.n > 0 ? probe.n : 1;
   chunk = (chunk + 63) & ~63LL;
 
+  // probe key columns of the slice [start, start+len); the Cols own nothing
+  // new but must outlive the bg_column views taken of them
+  auto slice_probe_keys = [&](int64_t start, int64_t len,
+                              std::vector<Col>& sliced,
+                              std::vector<bg_column>& views) {
+    for (int id : pk_ids) {
+      sliced.push_back(slice_col(probe.cols[(size_t)id], start, len));
+      views.push_back(to_bg(sliced.back(), len));
+    }
+  };
+
   auto& outputs = node.get_arr("output");
   std::vector<std::vector<Col>> pieces(outputs.size());
   std::vector<int64_t> piece_lens;
   int64_t total_matches = 0;
 
+  if (join_type == BG_JOIN_SEMI_BUILD || join_type == BG_JOIN_ANTI_BUILD) {
+    // only the visited bitmap matters: mark per probe chunk (no pair
+    // buffers), then list the build rows once, in ascending build order
+    for (auto& o : outputs) require_build_side(jt, *o);
+    for (int64_t start = 0; start < probe.n; start += chunk) {
+      const int64_t len = probe.n - start < chunk ? probe.n - start : chunk;
+      std::vector<bg_column> pk;
+      std::vector<Col> pk_sliced;
+      slice_probe_keys(start, len, pk_sliced, pk);
+      chk(bg_hashjoin_probe_mark2(guard.h, pk.data(), (int32_t)pk.size(),
+                                  len),
+          "bg_hashjoin_probe_mark2");
+    }
+    DBufPtr idx = dalloc((uint64_t)(build.n > 0 ? build.n : 1) * 4);
+    int64_t rows = 0;
+    chk(bg_hashjoin_build_rows2(guard.h,
+                                join_type == BG_JOIN_SEMI_BUILD ? 1 : 0,
+                                &rows, (uint32_t*)idx->p),
+        "bg_hashjoin_build_rows2");
+    Table out;
+    out.n = rows;
+    for (auto& o : outputs) {
+      const std::string col = o->get_str("col");
+      out.names.push_back(o->get_str_or("as", col));
+      out.cols.push_back(gather_col(build.cols[(size_t)build.idx(col)],
+                                    build.n, (const uint32_t*)idx->p, rows));
+    }
+    return out;
+  }
+  // the types whose unmatched probe rows carry BG_JOIN_NULL_IDX build ids
+  const bool probe_outer =
+      join_type == BG_JOIN_OUTER_PROBE || join_type == BG_JOIN_OUTER_FULL;
+
   for (int64_t start = 0; start < probe.n || (probe.n == 0 && start == 0);
        start += chunk) {
     const int64_t len =
         probe.n - start < chunk ? probe.n - start : chunk;
-    // sliced probe key columns
     std::vector<bg_column> pk;
     std::vector<Col> pk_sliced;
-    for (int id : pk_ids) {
-      pk_sliced.push_back(slice_col(probe.cols[(size_t)id], start, len));
-      pk.push_back(to_bg(pk_sliced.back(), len));
-    }
+    slice_probe_keys(start, len, pk_sliced, pk);
     int64_t matches = 0;
     if (fast_int64)
       chk(bg_hashjoin_probe_count(guard.h, &pk[0], len, &matches),
@@ -1481,7 +1558,7 @@ static Table exec_join(const Value& node, Metrics& m) {
           "bg_hashjoin_probe_fill2");
 
     DBufPtr bidx_clamped, outer_valid;
-    if (join_type == BG_JOIN_OUTER_PROBE) {
+    if (probe_outer) {
       bidx_clamped = dalloc((uint64_t)(matches > 0 ? matches : 1) * 4);
       outer_valid = dalloc((uint64_t)((matches + 63) / 64) * 8 + 8);
       chk(bg_memset(outer_valid->p, 0xFF, outer_valid->bytes), "bg_memset");
@@ -1494,10 +1571,13 @@ static Table exec_join(const Value& node, Metrics& m) {
       const Value& o = *outputs[oi];
       const std::string side = o.get_str("side");
       const std::string col = o.get_str("col");
-      const bool outer_build =
-          side == "build" && join_type == BG_JOIN_OUTER_PROBE;
+      const bool outer_build = side == "build" && probe_outer;
       Col c;
-      if (side == "build") {
+      if (outer_build && join_type == BG_JOIN_OUTER_FULL && build.n == 0) {
+        // full join over an empty build side: every pair is an unmatched
+        // probe row, and there is no build row 0 to gather a filler from
+        c = null_col(build.cols[(size_t)build.idx(col)], matches);
+      } else if (side == "build") {
         const uint32_t* idx =
             (const uint32_t*)(outer_build ? bidx_clamped->p : bidx->p);
         c = gather_col(build.cols[(size_t)build.idx(col)], build.n, idx,
@@ -1523,6 +1603,28 @@ static Table exec_join(const Value& node, Metrics& m) {
     piece_lens.push_back(matches);
     total_matches += matches;
     if (probe.n == 0) break;
+  }
+
+  if (join_type == BG_JOIN_OUTER_BUILD || join_type == BG_JOIN_OUTER_FULL) {
+    // one tail piece after the last chunk: the build rows no probe row
+    // matched, with NULL probe-side columns
+    DBufPtr idx = dalloc((uint64_t)(build.n > 0 ? build.n : 1) * 4);
+    int64_t rows = 0;
+    chk(bg_hashjoin_build_rows2(guard.h, 0, &rows, (uint32_t*)idx->p),
+        "bg_hashjoin_build_rows2");
+    for (size_t oi = 0; oi < outputs.size(); ++oi) {
+      const Value& o = *outputs[oi];
+      const std::string col = o.get_str("col");
+      if (o.get_str("side") == "build")
+        pieces[oi].push_back(gather_col(build.cols[(size_t)build.idx(col)],
+                                        build.n, (const uint32_t*)idx->p,
+                                        rows));
+      else
+        pieces[oi].push_back(
+            null_col(probe.cols[(size_t)probe.idx(col)], rows));
+    }
+    piece_lens.push_back(rows);
+    total_matches += rows;
   }
 
   Table out;
@@ -2728,10 +2830,14 @@ static VSchema validate_plan(const Value& node) {
     for (auto& k : node.get_arr("build_keys")) b.idx(k->s);
     for (auto& k : node.get_arr("probe_keys")) p.idx(k->s);
     const std::string jt = node.get_str_or("join_type", "inner");
-    if (jt != "inner" && jt != "semi" && jt != "anti" && jt != "left")
+    if (jt != "inner" && jt != "semi" && jt != "anti" && jt != "left" &&
+        jt != "semi_build" && jt != "anti_build" && jt != "outer_build" &&
+        jt != "full")
       throw StageError(BG_ERR_UNSUPPORTED, "hash_join: join_type " + jt);
+    const bool build_rows_only = jt == "semi_build" || jt == "anti_build";
     VSchema out;
     for (auto& o : node.get_arr("output")) {
+      if (build_rows_only) require_build_side(jt, *o);
       const VSchema& src = o->get_str("side") == "build" ? b : p;
       int i = src.idx(o->get_str("col"));
       out.names.push_back(o->get_str_or("as", o->get_str("col")));

@@ -176,6 +176,7 @@ _SIGNATURES = {
     "bg_hashjoin_free": "i p", "bg_hashjoin_build2": "i pilP",
     "bg_hashjoin_probe_count2": "i ppilip",
     "bg_hashjoin_probe_fill2": "i ppilipp", "bg_hashjoin_free2": "i p",
+    "bg_hashjoin_probe_mark2": "i ppil", "bg_hashjoin_build_rows2": "i pipp",
     "bg_idx_sentinel": "i plpp", "bg_bitmap_and": "i pplp",
     "bg_hashagg": "i pippipllpppp", "bg_hashagg2": "i pippipllppppp",
     "bg_project_dec128": "i ipplllp",

@@ -268,6 +268,42 @@ int bg_hashjoin_probe_fill2(void* handle, const bg_column* keys,
                             uint32_t* d_out_probe, uint32_t* d_out_build);
 int bg_hashjoin_free2(void* handle);
 
+/* ---- build-side-preserving join types ----
+ * DataFusion 55 HashJoinExec always builds on its LEFT input and tracks a
+ * per-build-row "visited" bitmap for the types that preserve it
+ * (joins/hash_join.rs: visited_left_side, emitted after the last probe
+ * batch).  With build = DataFusion's left input these restate LeftSemi /
+ * LeftAnti / Left / Full; SEMI/ANTI/OUTER_PROBE above are its RightSemi /
+ * RightAnti / Right.  The handle owns one visited bit per build row (Arrow
+ * LSB order, ((n_build+63)/64)*8 + 8 bytes), allocated and zeroed by the
+ * first marking call, accumulated over every later one, released by
+ * bg_hashjoin_free2.  Null semantics as above: a build row with any null
+ * key is never inserted, so never marked (ANTI_BUILD / OUTER_BUILD /
+ * OUTER_FULL emit it, SEMI_BUILD does not); a probe row with any null key
+ * marks nothing. */
+#define BG_JOIN_SEMI_BUILD  4  /* DataFusion LeftSemi: build rows with >=1 match, once */
+#define BG_JOIN_ANTI_BUILD  5  /* DataFusion LeftAnti: build rows with no match        */
+#define BG_JOIN_OUTER_BUILD 6  /* DataFusion Left:  inner pairs + unmatched build rows */
+#define BG_JOIN_OUTER_FULL  7  /* DataFusion Full:  OUTER_PROBE pairs + unmatched build rows */
+/* bg_hashjoin_probe_count2/_fill2 take types 6 and 7: the pairs are those
+ * of INNER / OUTER_PROBE, and fill2 also marks every matched build row;
+ * the unmatched build rows come from bg_hashjoin_build_rows2(matched=0)
+ * after the last probe chunk.  Types 4 and 5 emit no pairs: count2/fill2
+ * refuse them with BG_ERR_INVALID and point at bg_hashjoin_probe_mark2. */
+
+/* HashJoinExec's probe-side pass for LeftSemi/LeftAnti, where only the
+ * visited bitmap matters: mark only; emits nothing (types 4/5 need no pair
+ * buffers). Callable once per probe chunk. */
+int bg_hashjoin_probe_mark2(void* handle, const bg_column* keys, int32_t nkeys,
+                            int64_t n);
+
+/* HashJoinExec's final build-side emission (get_final_indices_from_bit_map):
+ * build rows whose visited bit == matched (0/1), ascending build index.
+ * d_out_build == NULL: count only. Bits at or beyond n_build are never
+ * reported. Valid before any marking call (then: nothing is matched). */
+int bg_hashjoin_build_rows2(void* handle, int32_t matched, int64_t* out_count,
+                            uint32_t* d_out_build);
+
 /* Split an index vector carrying BG_JOIN_NULL_IDX sentinels (probe-outer
  * build side) into a clamped gather-safe vector + the validity bitmap of
  * non-sentinel slots. */

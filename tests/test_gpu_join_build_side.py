@@ -1,0 +1,551 @@
+"""Build-side-preserving hash joins (DataFusion LeftSemi / LeftAnti / Left /
+Full with build = its left input): the visited bitmap behind
+bg_hashjoin_probe_mark2 / bg_hashjoin_build_rows2 and join types 6/7 at the
+C ABI, and semi_build / anti_build / outer_build / full through
+bg_execute_stage.  Every comparison is exact (index sets, pair arrays, row
+multisets) against a plain-Python recomputation with SQL null semantics:
+a NULL key matches nothing."""
+import ctypes
+import decimal
+import gc
+from collections import Counter, defaultdict
+
+import numpy as np
+import pyarrow as pa
+import pytest
+
+from datafusion_ballista_amd import gpu, stage
+
+pytestmark = pytest.mark.gpu
+
+BG_OK, BG_ERR_INVALID = 0, -3
+INNER, OUTER_PROBE = 0, 3
+SEMI_BUILD, ANTI_BUILD, OUTER_BUILD, OUTER_FULL = 4, 5, 6, 7
+I64 = ctypes.c_int64
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = gpu.GpuStageContext(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture()
+def reg(ctx):
+    keep, names = [], []
+
+    def _reg(name, table):
+        keep.append(stage.register_table(ctx, name, table))
+        names.append(name)
+        return table
+
+    yield _reg
+    for n in names:
+        stage.unregister_table(n)
+
+
+# ---------------------------------------------------------------------------
+# ABI level
+# ---------------------------------------------------------------------------
+def cols(*cs):
+    return (gpu.BgColumn * len(cs))(*cs)
+
+
+def valid_bytes(valid):
+    """bool[n] -> Arrow LSB validity, padded like every mask here."""
+    n = len(valid)
+    out = np.zeros((n + 63) // 64 * 8 + 8, dtype=np.uint8)
+    out[:(n + 7) // 8] = np.packbits(valid, bitorder="little")
+    return out
+
+
+def key_col(ctx, keys, valid=None):
+    col, _ = ctx.upload_column(
+        np.ascontiguousarray(keys, dtype=np.int64), gpu.BG_DT_INT64,
+        validity=None if valid is None else valid_bytes(valid))
+    return col
+
+
+class Join:
+    """One bg_hashjoin_build2 handle over a single Int64 key column."""
+
+    def __init__(self, ctx, bcol, n_build):
+        self.ctx, self.bcol, self.n_build = ctx, bcol, n_build
+        self.h = ctypes.c_void_p()
+        assert ctx.L.bg_hashjoin_build2(cols(bcol), 1, I64(n_build),
+                                        ctypes.byref(self.h)) == BG_OK
+
+    def mark(self, pcol, n):
+        assert self.ctx.L.bg_hashjoin_probe_mark2(
+            self.h, cols(pcol), 1, I64(n)) == BG_OK
+
+    def rows(self, matched):
+        """Count-only call, then the filled call; both must agree."""
+        L = self.ctx.L
+        cnt = I64(-1)
+        assert L.bg_hashjoin_build_rows2(self.h, matched, ctypes.byref(cnt),
+                                         None) == BG_OK
+        assert 0 <= cnt.value <= self.n_build
+        out = self.ctx.alloc(4 * self.n_build + 4)
+        out.upload(np.full(self.n_build + 1, 0xDEADBEEF, dtype=np.uint32))
+        cnt2 = I64(-1)
+        assert L.bg_hashjoin_build_rows2(self.h, matched, ctypes.byref(cnt2),
+                                         out.ptr) == BG_OK
+        assert cnt2.value == cnt.value
+        got = out.download(np.uint32, self.n_build + 1)
+        # nothing written past the reported count
+        assert np.all(got[cnt.value:] == 0xDEADBEEF)
+        return got[:cnt.value].astype(np.int64)
+
+    def pairs(self, pcol, n, join_type):
+        L = self.ctx.L
+        m = I64()
+        assert L.bg_hashjoin_probe_count2(self.h, cols(pcol), 1, I64(n),
+                                          join_type, ctypes.byref(m)) == BG_OK
+        op = self.ctx.alloc(4 * max(m.value, 1))
+        ob = self.ctx.alloc(4 * max(m.value, 1))
+        assert L.bg_hashjoin_probe_fill2(self.h, cols(pcol), 1, I64(n),
+                                         join_type, op.ptr, ob.ptr) == BG_OK
+        return (op.download(np.uint32, m.value),
+                ob.download(np.uint32, m.value))
+
+    def free(self):
+        assert self.ctx.L.bg_hashjoin_free2(self.h) == BG_OK
+        self.h = ctypes.c_void_p()
+
+
+def abi_case(n_build, seed):
+    """Duplicate build keys, ~10 % NULL build keys, ~10 % NULL probe keys,
+    build keys that no probe row carries (k % 5 == 3), probe keys that no
+    build row carries; the LAST build row is valid and probed, so the top
+    bit of the last bitmap word is exercised at every size."""
+    rng = np.random.default_rng(seed)
+    domain = max(2, n_build * 2 // 3)
+    bkeys = rng.integers(0, domain, size=n_build, dtype=np.int64)
+    bvalid = rng.random(n_build) >= 0.1
+    bkeys[-1], bvalid[-1] = 0, True
+    n_probe = 4 * n_build + 50
+    pkeys = rng.integers(0, domain + 5, size=n_probe, dtype=np.int64)
+    pkeys[pkeys % 5 == 3] = 0
+    pvalid = rng.random(n_probe) >= 0.1
+    pkeys[0], pvalid[0] = 0, True
+    probed = {int(k) for k, v in zip(pkeys, pvalid) if v}
+    matched = [i for i in range(n_build)
+               if bvalid[i] and int(bkeys[i]) in probed]
+    return bkeys, bvalid, pkeys, pvalid, matched
+
+
+@pytest.mark.parametrize("n_build", [1, 31, 32, 33, 63, 64, 65, 1000])
+def test_mark_and_build_rows(ctx, n_build):
+    bkeys, bvalid, pkeys, pvalid, matched = abi_case(n_build, seed=n_build)
+    j = Join(ctx, key_col(ctx, bkeys, bvalid), n_build)
+    try:
+        # before any marking call: nothing is matched
+        assert j.rows(1).tolist() == []
+        assert j.rows(0).tolist() == list(range(n_build))
+        j.mark(key_col(ctx, pkeys, pvalid), len(pkeys))
+        got1, got0 = j.rows(1), j.rows(0)
+        unmatched = sorted(set(range(n_build)) - set(matched))
+        assert got1.tolist() == matched            # ascending, exact
+        assert got0.tolist() == unmatched
+        assert not set(got1.tolist()) & set(got0.tolist())
+        assert sorted(got1.tolist() + got0.tolist()) == list(range(n_build))
+        if n_build >= 31:
+            # the case really has duplicates, NULL keys and unprobed keys
+            assert len(set(bkeys[bvalid].tolist())) < int(bvalid.sum())
+            assert not bvalid.all() and unmatched and matched
+    finally:
+        j.free()
+
+
+def test_contention_loses_no_bit(ctx):
+    """64 build rows = two 32-bit atomic words; 200 000 probe rows from 60
+    of the 64 keys: every wave ORs into the same two words."""
+    n_build, n_probe = 64, 200_000
+    absent = [5, 31, 32, 63]
+    present = np.array([k for k in range(n_build) if k not in absent],
+                       dtype=np.int64)
+    rng = np.random.default_rng(7)
+    pkeys = present[rng.integers(0, len(present), size=n_probe)]
+    j = Join(ctx, key_col(ctx, np.arange(n_build)), n_build)
+    try:
+        j.mark(key_col(ctx, pkeys), n_probe)
+        assert j.rows(1).tolist() == present.tolist()
+        assert j.rows(0).tolist() == absent
+    finally:
+        j.free()
+
+
+def test_marks_accumulate_across_calls(ctx):
+    n_build = 1000
+    bkeys, bvalid, pkeys, pvalid, matched = abi_case(n_build, seed=99)
+    bcol = key_col(ctx, bkeys, bvalid)
+    once = Join(ctx, bcol, n_build)
+    parts = Join(ctx, bcol, n_build)
+    try:
+        once.mark(key_col(ctx, pkeys, pvalid), len(pkeys))
+        seen = set()
+        for lo, hi in [(0, 1300), (1300, 1301), (1301, len(pkeys))]:
+            parts.mark(key_col(ctx, pkeys[lo:hi], pvalid[lo:hi]), hi - lo)
+            seen |= {int(k) for k, v in zip(pkeys[lo:hi], pvalid[lo:hi]) if v}
+            want = [i for i in range(n_build)
+                    if bvalid[i] and int(bkeys[i]) in seen]
+            assert parts.rows(1).tolist() == want
+        assert parts.rows(1).tolist() == once.rows(1).tolist() == matched
+        assert parts.rows(0).tolist() == once.rows(0).tolist()
+    finally:
+        once.free()
+        parts.free()
+
+
+@pytest.mark.parametrize("join_type", [SEMI_BUILD, ANTI_BUILD])
+def test_count_and_fill_refuse_build_rows_only_types(ctx, join_type):
+    n = 100
+    col = key_col(ctx, np.arange(n))
+    j = Join(ctx, col, n)
+    buf = ctx.alloc(4 * n)
+    try:
+        m = I64()
+        rc = ctx.L.bg_hashjoin_probe_count2(j.h, cols(col), 1, I64(n),
+                                            join_type, ctypes.byref(m))
+        assert rc == BG_ERR_INVALID
+        assert b"bg_hashjoin_probe_mark2" in ctx.L.bg_last_error()
+        rc = ctx.L.bg_hashjoin_probe_fill2(j.h, cols(col), 1, I64(n),
+                                           join_type, buf.ptr, buf.ptr)
+        assert rc == BG_ERR_INVALID
+        assert b"bg_hashjoin_probe_mark2" in ctx.L.bg_last_error()
+    finally:
+        j.free()
+
+
+def test_pool_balance(ctx):
+    """Only the bitmap may stay live: the first marking call adds exactly
+    one buffer, a second one and build_rows2 add nothing, and free2 gives
+    everything back."""
+    n = 1000
+    bcol = key_col(ctx, np.arange(n))
+    pcol = key_col(ctx, np.arange(0, 2 * n, 2))
+    out = ctx.alloc(4 * n)
+    cnt = I64()
+    L = ctx.L
+
+    def balanced(call):
+        gc.collect()
+        before = ctx.pool_stats()[:2]
+        ret = call()
+        assert ctx.pool_stats()[:2] == before
+        return ret
+
+    gc.collect()
+    base = ctx.pool_stats()[:2]
+    h = ctypes.c_void_p()
+    assert L.bg_hashjoin_build2(cols(bcol), 1, I64(n),
+                                ctypes.byref(h)) == BG_OK
+    built = ctx.pool_stats()[:2]
+    assert built[1] == base[1] + 2                 # nodes + head, no bitmap
+    # valid before any marking call, and allocates nothing
+    assert balanced(lambda: L.bg_hashjoin_build_rows2(
+        h, 0, ctypes.byref(cnt), out.ptr)) == BG_OK and cnt.value == n
+    assert L.bg_hashjoin_probe_mark2(h, cols(pcol), 1, I64(n)) == BG_OK
+    assert ctx.pool_stats()[1] == built[1] + 1     # + the bitmap
+    assert balanced(lambda: L.bg_hashjoin_probe_mark2(
+        h, cols(pcol), 1, I64(n))) == BG_OK
+    for matched in (1, 0):
+        assert balanced(lambda: L.bg_hashjoin_build_rows2(
+            h, matched, ctypes.byref(cnt), out.ptr)) == BG_OK
+        assert cnt.value == n // 2
+        assert balanced(lambda: L.bg_hashjoin_build_rows2(
+            h, matched, ctypes.byref(cnt), None)) == BG_OK
+    assert L.bg_hashjoin_free2(h) == BG_OK
+    gc.collect()
+    assert ctx.pool_stats()[:2] == base
+
+
+def test_marking_types_emit_the_pairs_of_the_types_they_extend(ctx):
+    n_build = 1000
+    bkeys, bvalid, pkeys, pvalid, matched = abi_case(n_build, seed=5)
+    j = Join(ctx, key_col(ctx, bkeys, bvalid), n_build)
+    pcol = key_col(ctx, pkeys, pvalid)
+    try:
+        built = ctx.pool_stats()[1]
+        ip, ib = j.pairs(pcol, len(pkeys), INNER)
+        lp, lb = j.pairs(pcol, len(pkeys), OUTER_PROBE)
+        # the four existing types never allocate the bitmap (+1 = offsets)
+        gc.collect()
+        assert ctx.pool_stats()[1] == built + 1
+        assert j.rows(1).tolist() == []
+        p6, b6 = j.pairs(pcol, len(pkeys), OUTER_BUILD)
+        assert np.array_equal(p6, ip) and np.array_equal(b6, ib)
+        assert j.rows(1).tolist() == matched       # fill 6 marked
+        assert sorted(set(ib.tolist())) == matched
+        p7, b7 = j.pairs(pcol, len(pkeys), OUTER_FULL)
+        assert np.array_equal(p7, lp) and np.array_equal(b7, lb)
+        assert len(lp) > len(ip)                   # has unmatched probe rows
+    finally:
+        j.free()
+    # and type 7 marks on its own, on a fresh handle
+    j = Join(ctx, key_col(ctx, bkeys, bvalid), n_build)
+    try:
+        j.pairs(pcol, len(pkeys), OUTER_FULL)
+        assert j.rows(1).tolist() == matched
+    finally:
+        j.free()
+
+
+# ---------------------------------------------------------------------------
+# stage level
+# ---------------------------------------------------------------------------
+def _doc(plan):
+    return {"job_id": "job-jbs", "stage_id": 1, "task_id": 0,
+            "work_dir": "/tmp/stage-tests", "plan": plan}
+
+
+def scan_of(table, name):
+    return {"op": "scan", "schema": stage.schema_json(table.schema),
+            "source": {"kind": "device", "table": name}}
+
+
+def dec_array(unscaled, mask):
+    return pa.array([None if m else decimal.Decimal(int(v)) / 100
+                     for v, m in zip(unscaled, mask)],
+                    type=pa.decimal128(15, 2))
+
+
+def make_sides(nb, np_, seed):
+    """-> (build table, probe table, build rows, probe rows); a row is
+    (k1, k2, id, dec, str) in the form bg_execute_stage reports: decimals as
+    unscaled integer strings, NULL as None.  k1 has duplicates and ~10 %
+    NULLs on both sides, odd k1 values appear on the build side only, and k2
+    is drawn independently, so the composite key rejects k1-only matches."""
+    rng = np.random.default_rng(seed)
+    bk = rng.integers(0, nb // 2, size=nb, dtype=np.int64) * 2
+    bk[rng.random(nb) < 0.25] += 1                     # never probed
+    pk = rng.integers(0, nb // 2 + 40, size=np_, dtype=np.int64) * 2
+    bkm, pkm = rng.random(nb) < 0.1, rng.random(np_) < 0.1
+    out = []
+    for n, k, km, tag in ((nb, bk, bkm, "b"), (np_, pk, pkm, "p")):
+        k2 = [f"s{v}" for v in rng.integers(0, 3, size=n)]
+        dec = rng.integers(-10**6, 10**6, size=n)
+        dm = rng.random(n) < 0.2
+        st = [None if i % 7 == 3 else f"{tag}{i % 97}" * (i % 3) for i in
+              range(n)]
+        t = pa.table({
+            f"{tag}k1": pa.array(k, mask=km),
+            f"{tag}k2": pa.array(k2),
+            f"{tag}id": pa.array(np.arange(n, dtype=np.int64)),
+            f"{tag}dec": dec_array(dec, dm),
+            f"{tag}str": pa.array(st, type=pa.string()),
+        })
+        rows = [(None if km[i] else int(k[i]), k2[i], i,
+                 None if dm[i] else str(int(dec[i])), st[i])
+                for i in range(n)]
+        out.append((t, rows))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
+
+
+def reference(brows, prows, nkeys):
+    """-> {join type: list of output rows}; outputs are bid, bdec, bstr
+    (+ pid, pdec, pstr for the outer types)."""
+    def key(r):
+        return None if r[0] is None else r[:nkeys]
+
+    index = defaultdict(list)
+    for r in brows:
+        if key(r) is not None:
+            index[key(r)].append(r)
+    inner, lone_probe, hit = [], [], set()
+    for p in prows:
+        ms = index.get(key(p), []) if key(p) is not None else []
+        for b in ms:
+            inner.append(b[2:] + p[2:])
+            hit.add(b[2])
+        if not ms:
+            lone_probe.append((None, None, None) + p[2:])
+    lone_build = [b[2:] + (None, None, None) for b in brows
+                  if b[2] not in hit]
+    return {
+        "semi_build": [b[2:] for b in brows if b[2] in hit],
+        "anti_build": [b[2:] for b in brows if b[2] not in hit],
+        "outer_build": inner + lone_build,
+        "full": inner + lone_probe + lone_build,
+    }
+
+
+def join_plan(bscan, pscan, nkeys, jt, chunk=0):
+    output = [{"side": "build", "col": c} for c in ("bid", "bdec", "bstr")]
+    if jt in ("outer_build", "full"):
+        output += [{"side": "probe", "col": c}
+                   for c in ("pid", "pdec", "pstr")]
+    plan = {"op": "hash_join", "build": bscan, "probe": pscan,
+            "build_keys": ["bk1", "bk2"][:nkeys],
+            "probe_keys": ["pk1", "pk2"][:nkeys],
+            "join_type": jt, "output": output}
+    if chunk:
+        plan["probe_chunk_rows"] = chunk
+    return {"op": "collect", "input": plan}
+
+
+def run(plan):
+    return [tuple(r) for r in stage.execute(_doc(plan))["rows"]]
+
+
+JOIN_TYPES = ["semi_build", "anti_build", "outer_build", "full"]
+
+
+@pytest.fixture(scope="module")
+def sides_500():
+    return make_sides(500, 20_000, seed=61)
+
+
+@pytest.mark.parametrize("nkeys", [1, 2], ids=["int64", "int64+utf8"])
+def test_stage_all_types(ctx, reg, sides_500, nkeys):
+    build, probe, brows, prows = sides_500
+    reg("jbs_b", build)
+    reg("jbs_p", probe)
+    want = reference(brows, prows, nkeys)
+    assert want["semi_build"] and want["anti_build"]
+    for jt in JOIN_TYPES:
+        got = run(join_plan(scan_of(build, "jbs_b"), scan_of(probe, "jbs_p"),
+                            nkeys, jt))
+        if jt in ("semi_build", "anti_build"):
+            assert got == want[jt], jt             # ascending build order
+        else:
+            assert Counter(got) == Counter(want[jt]), jt
+
+
+def test_stage_chunked_matches_unchunked(ctx, reg):
+    build, probe, brows, prows = make_sides(700, 25_000, seed=67)
+    reg("jbc_b", build)
+    reg("jbc_p", probe)
+    want = reference(brows, prows, 1)
+    for jt in JOIN_TYPES:
+        whole, chunked = (run(join_plan(
+            scan_of(build, "jbc_b"), scan_of(probe, "jbc_p"), 1, jt, chunk))
+            for chunk in (0, 4096))
+        assert Counter(chunked) == Counter(whole) == Counter(want[jt]), jt
+        if jt in ("outer_build", "full"):
+            # the unmatched-build tail appears exactly once
+            tail = Counter(r for r in chunked if r[3] is None)
+            assert tail == Counter(r for r in want[jt] if r[3] is None)
+            assert all(c == 1 for c in tail.values()) and tail
+
+
+@pytest.mark.parametrize("empty", ["probe", "build"])
+def test_stage_empty_side(ctx, reg, empty):
+    """The empty side is a filter that keeps no row."""
+    build, probe, brows, prows = make_sides(300, 1_000, seed=71)
+    reg("jbe_b", build)
+    reg("jbe_p", probe)
+    bscan, pscan = scan_of(build, "jbe_b"), scan_of(probe, "jbe_p")
+    none = lambda scan, col: {"op": "filter", "input": scan, "predicates": [  # noqa: E731
+        {"col": col, "cmp": "lt", "hi": -1}]}
+    if empty == "probe":
+        pscan, prows = none(pscan, "pid"), []
+    else:
+        bscan, brows = none(bscan, "bid"), []
+    want = reference(brows, prows, 1)
+    if empty == "probe":
+        every = [b[2:] for b in brows]
+        assert want["semi_build"] == [] and want["anti_build"] == every
+        assert want["outer_build"] == want["full"] == \
+            [r + (None, None, None) for r in every]
+    else:
+        assert want["semi_build"] == want["anti_build"] == \
+            want["outer_build"] == []
+        assert want["full"] == [(None, None, None) + p[2:] for p in prows]
+    for jt in JOIN_TYPES:
+        got = run(join_plan(bscan, pscan, 1, jt))
+        assert Counter(got) == Counter(want[jt]), jt
+        assert len(got) == len(want[jt])
+
+
+def test_probe_side_output_is_refused_at_execution(ctx, reg, sides_500):
+    build, probe, _, _ = sides_500
+    reg("jbr_b", build)
+    reg("jbr_p", probe)
+    for jt in ("semi_build", "anti_build"):
+        plan = join_plan(scan_of(build, "jbr_b"), scan_of(probe, "jbr_p"),
+                         1, jt)
+        plan["input"]["output"].append({"side": "probe", "col": "pid"})
+        with pytest.raises(RuntimeError, match=r"rc=-3.*build rows only"):
+            stage.execute(_doc(plan))
+
+
+# ---------------------------------------------------------------------------
+# plan shapes
+# ---------------------------------------------------------------------------
+def test_q4_shape(ctx, reg):
+    """orders (date-filtered) semi_build lineitem, then count by priority:
+    the hash table goes on orders, each order counts once."""
+    rng = np.random.default_rng(73)
+    n_o, n_l = 3_000, 12_000
+    odate = rng.integers(8000, 9000, size=n_o).astype(np.int32)
+    oprio = rng.integers(0, 5, size=n_o, dtype=np.int64)
+    orders = pa.table({"o_orderkey": pa.array(np.arange(n_o, dtype=np.int64)),
+                       "o_orderdate": pa.array(odate, type=pa.date32()),
+                       "o_orderpriority": pa.array(oprio)})
+    lkey = rng.integers(0, n_o, size=n_l, dtype=np.int64)
+    commit = rng.integers(0, 100, size=n_l, dtype=np.int64)
+    receipt = rng.integers(0, 100, size=n_l, dtype=np.int64)
+    late = (commit < receipt).astype(np.int64)
+    lineitem = pa.table({"l_orderkey": pa.array(lkey),
+                         "l_late": pa.array(late)})
+    reg("q4_o", orders)
+    reg("q4_l", lineitem)
+    lo, hi = 8300, 8392
+    plan = {"op": "collect", "input": {
+        "op": "hash_aggregate", "mode": "single",
+        "group_by": ["o_orderpriority"],
+        "aggs": [{"fn": "count", "as": "order_count"}],
+        "input": {
+            "op": "hash_join", "join_type": "semi_build",
+            "build": {"op": "filter", "input": scan_of(orders, "q4_o"),
+                      "predicates": [{"col": "o_orderdate", "cmp": "ge_lt",
+                                      "lo": lo, "hi": hi}]},
+            "probe": {"op": "filter", "input": scan_of(lineitem, "q4_l"),
+                      "predicates": [{"col": "l_late", "cmp": "eq",
+                                      "lo": 1, "hi": 1}]},
+            "build_keys": ["o_orderkey"], "probe_keys": ["l_orderkey"],
+            "output": [{"side": "build", "col": "o_orderpriority"}]}}}
+    got = sorted(run(plan))
+    late_orders = {int(k) for k, f in zip(lkey, late) if f}
+    want = Counter(int(oprio[o]) for o in range(n_o)
+                   if lo <= odate[o] < hi and o in late_orders)
+    assert got == sorted(want.items()) and len(want) == 5
+
+
+def test_q13_shape(ctx, reg):
+    """customer outer_build orders, count(o_orderkey) per customer (NULLs
+    skipped: customers without orders count 0), then the histogram."""
+    rng = np.random.default_rng(79)
+    n_c, n_o = 2_000, 20_000
+    customer = pa.table({"c_custkey": pa.array(np.arange(n_c,
+                                                         dtype=np.int64))})
+    # every third customer places no order
+    buyers = np.array([c for c in range(n_c) if c % 3], dtype=np.int64)
+    ocust = buyers[rng.integers(0, len(buyers), size=n_o)]
+    orders = pa.table({"o_orderkey": pa.array(np.arange(n_o, dtype=np.int64)),
+                       "o_custkey": pa.array(ocust)})
+    reg("q13_c", customer)
+    reg("q13_o", orders)
+    per_cust = {"op": "hash_aggregate", "mode": "single",
+                "group_by": ["c_custkey"],
+                "aggs": [{"fn": "count", "as": "c_count",
+                          "expr": {"col": "o_orderkey"}}],
+                "input": {
+                    "op": "hash_join", "join_type": "outer_build",
+                    "build": scan_of(customer, "q13_c"),
+                    "probe": scan_of(orders, "q13_o"),
+                    "build_keys": ["c_custkey"], "probe_keys": ["o_custkey"],
+                    "probe_chunk_rows": 8192,
+                    "output": [{"side": "build", "col": "c_custkey"},
+                               {"side": "probe", "col": "o_orderkey"}]}}
+    plan = {"op": "collect", "input": {
+        "op": "hash_aggregate", "mode": "single", "group_by": ["c_count"],
+        "aggs": [{"fn": "count", "as": "custdist"}], "input": per_cust}}
+    got = sorted(run(plan))
+    orders_of = Counter(int(c) for c in ocust)
+    want = Counter(orders_of.get(c, 0) for c in range(n_c))
+    assert got == sorted(want.items())
+    assert want[0] >= n_c // 3
