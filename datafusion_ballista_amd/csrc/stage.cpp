@@ -37,6 +37,7 @@
 #include <sys/stat.h>
 #include <sys/types.h>
 
+#include <algorithm>
 #include <cerrno>
 #include <chrono>
 #include <cstdint>
@@ -92,10 +93,32 @@ using DBufPtr = std::shared_ptr<DBuf>;
 
 static DBufPtr dalloc(uint64_t n) { return std::make_shared<DBuf>(n); }
 
+// n elements of esz bytes each; an empty column still owns one element
+static DBufPtr dalloc_elems(int64_t n, int64_t esz = 1) {
+  return dalloc((uint64_t)(n > 0 ? n : 1) * (uint64_t)esz);
+}
+
+// Padded bitmap of nbits bits (validity, filter masks): whole 64-bit words
+// plus one spare, so word-wide kernels may touch the word after the last
+// bit.  join_visited_bytes() in kernels.hip uses the same formula for the
+// join's visited bitmap.  fill >= 0 memsets every byte to it.
+static DBufPtr alloc_bitmap(int64_t nbits, int fill = -1) {
+  DBufPtr b = dalloc((uint64_t)((nbits + 63) / 64) * 8 + 8);
+  if (fill >= 0) chk(bg_memset(b->p, fill, b->bytes), "bg_memset");
+  return b;
+}
+
 static DBufPtr upload(const void* host, uint64_t n) {
   DBufPtr b = dalloc(n);
   if (n) chk(bg_memcpy_h2d(b->p, host, n), "bg_memcpy_h2d");
   return b;
+}
+
+using Clock = std::chrono::steady_clock;
+static int64_t ns_since(Clock::time_point t0) {
+  return std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() -
+                                                              t0)
+      .count();
 }
 
 static int64_t dt_size(int32_t dt) {
@@ -110,6 +133,9 @@ static int64_t dt_size(int32_t dt) {
     default: throw StageError(BG_ERR_INVALID, "unknown dtype tag");
   }
 }
+
+// a dtype as the plan JSON spells it (Arrow vocabulary)
+struct DtSpec { int32_t dt, precision, scale; };
 
 struct Col {
   int32_t dtype = 0;
@@ -128,7 +154,17 @@ struct Col {
     return offsets ? (const int32_t*)offsets->p : ext_offs;
   }
   bool nullable() const { return vptr() != nullptr; }
+  DtSpec spec() const { return {dtype, precision, scale}; }
 };
+
+// a Col of the given type that owns no buffers yet
+static Col make_col(const DtSpec& d) {
+  Col c;
+  c.dtype = d.dt;
+  c.precision = d.precision;
+  c.scale = d.scale;
+  return c;
+}
 
 struct Table {
   int64_t n = 0;
@@ -139,6 +175,10 @@ struct Table {
     for (size_t i = 0; i < names.size(); ++i)
       if (names[i] == name) return (int)i;
     throw StageError(BG_ERR_INVALID, "plan: unknown column '" + name + "'");
+  }
+  Col& col(const std::string& name) { return cols[(size_t)idx(name)]; }
+  const Col& col(const std::string& name) const {
+    return cols[(size_t)idx(name)];
   }
 };
 
@@ -155,8 +195,6 @@ static bg_column to_bg(const Col& c, int64_t n) {
 }
 
 // ---- dtype names in the plan JSON (Arrow vocabulary) ----
-struct DtSpec { int32_t dt, precision, scale; };
-
 static DtSpec parse_dtype(const Value& field) {
   const std::string& s = field.get_str("dtype");
   if (s == "int32") return {BG_DT_INT32, 0, 0};
@@ -219,10 +257,7 @@ static std::map<std::string, Table> g_tables;
 
 static Col gather_col(const Col& c, int64_t n_src, const uint32_t* d_idx,
                       int64_t m) {
-  Col out;
-  out.dtype = c.dtype;
-  out.precision = c.precision;
-  out.scale = c.scale;
+  Col out = make_col(c.spec());
   if (c.dtype == BG_DT_UTF8) {
     out.offsets = dalloc((uint64_t)(m + 1) * 4);
     // one-to-many joins can duplicate rows, so the gathered payload may
@@ -232,7 +267,7 @@ static Col gather_col(const Col& c, int64_t n_src, const uint32_t* d_idx,
     chk(bg_gather_varlen(c.dptr(), c.optr(), d_idx, m,
                          (int32_t*)out.offsets->p, nullptr, 0, &total),
         "bg_gather_varlen(size)");
-    out.data = dalloc((uint64_t)(total > 0 ? total : 1));
+    out.data = dalloc_elems(total);
     chk(bg_gather_varlen(c.dptr(), c.optr(), d_idx, m,
                          (int32_t*)out.offsets->p, out.data->p,
                          total > 0 ? total : 1, &total),
@@ -240,11 +275,11 @@ static Col gather_col(const Col& c, int64_t n_src, const uint32_t* d_idx,
     out.data_bytes = total;
   } else {
     int64_t esz = dt_size(c.dtype);
-    out.data = dalloc((uint64_t)(m > 0 ? m : 1) * (uint64_t)esz);
+    out.data = dalloc_elems(m, esz);
     chk(bg_gather(c.dptr(), esz, d_idx, m, out.data->p), "bg_gather");
   }
   if (c.nullable()) {
-    out.validity = dalloc((uint64_t)((m + 63) / 64) * 8 + 8);
+    out.validity = alloc_bitmap(m);
     chk(bg_gather_bits(c.vptr(), d_idx, m, out.validity->u8()),
         "bg_gather_bits");
   }
@@ -285,33 +320,25 @@ static Col slice_col(const Col& c, int64_t start, int64_t len) {
 // offsets, 0 data bytes): the NULL-extended side of an outer join's
 // unmatched rows.
 static Col null_col(const Col& like, int64_t m) {
-  Col out;
-  out.dtype = like.dtype;
-  out.precision = like.precision;
-  out.scale = like.scale;
+  Col out = make_col(like.spec());
   if (like.dtype == BG_DT_UTF8) {
     out.offsets = dalloc((uint64_t)(m + 1) * 4);
     chk(bg_memset(out.offsets->p, 0, out.offsets->bytes), "bg_memset");
     out.data = dalloc(1);
     out.data_bytes = 0;
   } else {
-    const int64_t esz = dt_size(like.dtype);
-    out.data = dalloc((uint64_t)(m > 0 ? m : 1) * (uint64_t)esz);
+    out.data = dalloc_elems(m, dt_size(like.dtype));
     chk(bg_memset(out.data->p, 0, out.data->bytes), "bg_memset");
   }
-  out.validity = dalloc((uint64_t)((m + 63) / 64) * 8 + 8);
-  chk(bg_memset(out.validity->p, 0, out.validity->bytes), "bg_memset");
+  out.validity = alloc_bitmap(m, 0);
   return out;
 }
 
 // Concatenate row-aligned column pieces (the chunked-probe merge).
 static Col concat_cols(const std::vector<Col>& pieces,
                        const std::vector<int64_t>& lens) {
-  Col out;
   const Col& c0 = pieces[0];
-  out.dtype = c0.dtype;
-  out.precision = c0.precision;
-  out.scale = c0.scale;
+  Col out = make_col(c0.spec());
   int64_t total = 0;
   bool any_null = false;
   for (size_t i = 0; i < pieces.size(); ++i) {
@@ -322,7 +349,7 @@ static Col concat_cols(const std::vector<Col>& pieces,
     int64_t bytes = 0;
     for (auto& p : pieces) bytes += p.data_bytes;
     out.offsets = dalloc((uint64_t)(total + 1) * 4);
-    out.data = dalloc((uint64_t)(bytes > 0 ? bytes : 1));
+    out.data = dalloc_elems(bytes);
     out.data_bytes = bytes;
     int64_t row = 0, db = 0;
     for (size_t i = 0; i < pieces.size(); ++i) {
@@ -342,7 +369,7 @@ static Col concat_cols(const std::vector<Col>& pieces,
     }
   } else {
     const int64_t esz = dt_size(c0.dtype);
-    out.data = dalloc((uint64_t)(total > 0 ? total : 1) * (uint64_t)esz);
+    out.data = dalloc_elems(total, esz);
     int64_t row = 0;
     for (size_t i = 0; i < pieces.size(); ++i) {
       if (lens[i])
@@ -353,8 +380,7 @@ static Col concat_cols(const std::vector<Col>& pieces,
     }
   }
   if (any_null) {
-    out.validity = dalloc((uint64_t)((total + 63) / 64) * 8 + 8);
-    chk(bg_memset(out.validity->p, 0xFF, out.validity->bytes), "bg_memset");
+    out.validity = alloc_bitmap(total, 0xFF);
     int64_t row = 0;
     for (size_t i = 0; i < pieces.size(); ++i) {
       if (lens[i] && pieces[i].nullable())
@@ -417,37 +443,75 @@ struct BatchSrc {
   int64_t raw_base;  // offset of this batch's stream range in the upload
 };
 
-static Table read_shuffle_locations(const std::vector<Value*>& locations,
-                                    const std::vector<DtSpec>& dts,
-                                    const std::vector<std::string>& names) {
-  // gather all partition ranges into one host buffer, remembering bases
-  std::vector<uint8_t> all;
-  std::vector<std::pair<int64_t, int64_t>> ranges;  // (base, len)
+// What the steps of one shuffle read share.
+struct ShuffleRead {
+  explicit ShuffleRead(const std::vector<DtSpec>& d) : dts(d) {}
+  const std::vector<DtSpec>& dts;
+  std::vector<uint8_t> all;       // every partition range, back to back
+  std::vector<BatchSrc> batches;
+  std::vector<size_t> first_buf;  // column -> index of its validity buffer
+  int64_t total = 0;              // rows over all batches
+  DBufPtr raw_dev;                // `all` on device
+  std::vector<int64_t> utf8_total;
+  std::vector<bg_lz4_frame> frames;  // one batched decompress
+  std::vector<int64_t> expect;       // decoded bytes each frame must give
+
+  // compressed buffer = [i64 usize][LZ4 frame]; read usize from host copy
+  int64_t usize_of(const BatchSrc& b, const bgipc::BufSpec& sp) const {
+    int64_t u;
+    memcpy(&u, all.data() + b.raw_base + sp.off, 8);
+    return u;
+  }
+  // real decoded bytes of a buffer (-1 prefix = stored raw, Arrow spec)
+  int64_t real_usize(const BatchSrc& b, const bgipc::BufSpec& sp) const {
+    if (!b.compressed) return sp.len;
+    int64_t u = usize_of(b, sp);
+    return u == -1 ? sp.len - 8 : u;
+  }
+};
+
+// validity bits / utf8 offsets land in scratch first and are placed after
+// the decompress
+struct ShuffleFixup {
+  int kind;  // 0 validity bitcopy, 1 utf8 offsets place
+  size_t c;
+  DBufPtr scratch;
+  int64_t rows, row_cursor, data_cursor;
+};
+
+// gather all partition ranges into one host buffer, remembering (base, len)
+static std::vector<std::pair<int64_t, int64_t>> gather_ranges(
+    const std::vector<Value*>& locations, std::vector<uint8_t>& all) {
+  std::vector<std::pair<int64_t, int64_t>> ranges;
+  auto append = [&](const std::vector<uint8_t>& raw) {
+    ranges.push_back({(int64_t)all.size(), (int64_t)raw.size()});
+    all.insert(all.end(), raw.begin(), raw.end());
+  };
   for (auto* loc : locations) {
     const std::string& data = loc->get_str("data");
     std::vector<int64_t> parts;
     if (loc->has("partition")) parts.push_back(loc->get_int("partition"));
     if (loc->has("partitions"))
       for (auto& p : loc->get_arr("partitions")) parts.push_back(p->i);
-    if (loc->has("index")) {
-      auto idx = read_index_file(loc->get_str("index"));
-      for (int64_t p : parts) {
-        if (p + 1 >= (int64_t)idx.size())
-          throw StageError(BG_ERR_INVALID, "partition out of index range");
-        auto raw = read_file_range(data, idx[(size_t)p],
-                                   idx[(size_t)p + 1] - idx[(size_t)p]);
-        ranges.push_back({(int64_t)all.size(), (int64_t)raw.size()});
-        all.insert(all.end(), raw.begin(), raw.end());
-      }
-    } else {
+    if (!loc->has("index")) {
       // whole file = one complete IPC stream (passthrough writer output)
-      auto raw = read_file_range(data, 0, -1);
-      ranges.push_back({(int64_t)all.size(), (int64_t)raw.size()});
-      all.insert(all.end(), raw.begin(), raw.end());
+      append(read_file_range(data, 0, -1));
+      continue;
+    }
+    auto idx = read_index_file(loc->get_str("index"));
+    for (int64_t p : parts) {
+      if (p + 1 >= (int64_t)idx.size())
+        throw StageError(BG_ERR_INVALID, "partition out of index range");
+      append(read_file_range(data, idx[(size_t)p],
+                             idx[(size_t)p + 1] - idx[(size_t)p]));
     }
   }
+  return ranges;
+}
 
-  size_t ncols = dts.size();
+static std::vector<BatchSrc> walk_batches(
+    const std::vector<uint8_t>& all,
+    const std::vector<std::pair<int64_t, int64_t>>& ranges, size_t ncols) {
   std::vector<BatchSrc> batches;
   for (auto& r : ranges) {
     auto metas = bgipc::walk_partition(all.data() + r.first, r.second);
@@ -455,180 +519,102 @@ static Table read_shuffle_locations(const std::vector<Value*>& locations,
       if (bm.bufs.size() < 2 * ncols)
         throw StageError(BG_ERR_INVALID,
                          "shuffle batch has fewer buffers than schema");
-      BatchSrc bs;
-      bs.rows = bm.n_rows;
-      bs.compressed = bm.compressed;
-      bs.raw_base = r.first + bm.body_off;
-      bs.bufs = bm.bufs;
-      batches.push_back(bs);
+      batches.push_back(
+          {bm.n_rows, bm.bufs, bm.compressed, r.first + bm.body_off});
     }
   }
+  return batches;
+}
 
-  int64_t total = 0;
-  for (auto& b : batches) total += b.rows;
-
-  Table out;
-  out.n = total;
-  out.names = names;
-  if (total == 0) {
-    for (size_t c = 0; c < ncols; ++c) {
-      Col col;
-      col.dtype = dts[c].dt;
-      col.precision = dts[c].precision;
-      col.scale = dts[c].scale;
-      col.data = dalloc(16);
-      if (col.dtype == BG_DT_UTF8) {
-        col.offsets = dalloc(4);
-        chk(bg_memset(col.offsets->p, 0, 4), "bg_memset");
-      }
-      out.cols.push_back(std::move(col));
-    }
-    return out;
-  }
-
-  DBufPtr raw_dev = upload(all.data(), all.size());
-
-  // which columns carry any validity buffer?
+// allocate the output columns: validity only where some batch carries one,
+// utf8 data sized from the sum of the data buffers' decoded sizes
+static void alloc_shuffle_columns(ShuffleRead& sr, Table& out) {
+  const size_t ncols = sr.dts.size();
   std::vector<bool> has_null(ncols, false);
-  for (auto& b : batches) {
-    size_t bi = 0;
-    for (size_t c = 0; c < ncols; ++c) {
-      if (b.bufs[bi].len > 0) has_null[c] = true;
-      bi += (dts[c].dt == BG_DT_UTF8) ? 3 : 2;
-    }
-  }
+  for (auto& b : sr.batches)
+    for (size_t c = 0; c < ncols; ++c)
+      if (b.bufs[sr.first_buf[c]].len > 0) has_null[c] = true;
 
-  // allocate columns
   for (size_t c = 0; c < ncols; ++c) {
-    Col col;
-    col.dtype = dts[c].dt;
-    col.precision = dts[c].precision;
-    col.scale = dts[c].scale;
-    if (col.dtype == BG_DT_UTF8) {
-      col.offsets = dalloc((uint64_t)(total + 1) * 4);
-      // size the data buffer from the sum of data-buffer uncompressed sizes
-      col.data = nullptr;  // set below after sizing
-    } else {
-      col.data = dalloc((uint64_t)total * (uint64_t)dt_size(col.dtype));
-    }
-    if (has_null[c]) {
-      col.validity = dalloc((uint64_t)((total + 63) / 64) * 8 + 8);
-      chk(bg_memset(col.validity->p, 0xFF, col.validity->bytes), "bg_memset");
-    }
+    Col col = make_col(sr.dts[c]);
+    if (col.dtype == BG_DT_UTF8)
+      col.offsets = dalloc((uint64_t)(sr.total + 1) * 4);  // data: below
+    else
+      col.data = dalloc((uint64_t)sr.total * (uint64_t)dt_size(col.dtype));
+    if (has_null[c]) col.validity = alloc_bitmap(sr.total, 0xFF);
     out.cols.push_back(std::move(col));
   }
 
-  // compressed buffer = [i64 usize][LZ4 frame]; read usize from host copy
-  auto usize_of = [&](const BatchSrc& b, const bgipc::BufSpec& sp) -> int64_t {
-    int64_t u;
-    memcpy(&u, all.data() + b.raw_base + sp.off, 8);
-    return u;
-  };
-  // real decoded bytes of a buffer (-1 prefix = stored raw, Arrow spec)
-  auto real_usize = [&](const BatchSrc& b,
-                        const bgipc::BufSpec& sp) -> int64_t {
-    if (!b.compressed) return sp.len;
-    int64_t u = usize_of(b, sp);
-    return u == -1 ? sp.len - 8 : u;
-  };
-
-  // size utf8 data buffers
-  std::vector<int64_t> utf8_total(ncols, 0);
+  sr.utf8_total.assign(ncols, 0);
   for (size_t c = 0; c < ncols; ++c) {
-    if (dts[c].dt != BG_DT_UTF8) continue;
-    for (auto& b : batches) {
-      size_t bi = 0;
-      for (size_t cc = 0; cc < c; ++cc)
-        bi += (dts[cc].dt == BG_DT_UTF8) ? 3 : 2;
-      auto& dsp = b.bufs[bi + 2];
-      if (dsp.len == 0) continue;
-      utf8_total[c] += real_usize(b, dsp);
+    if (sr.dts[c].dt != BG_DT_UTF8) continue;
+    for (auto& b : sr.batches) {
+      auto& dsp = b.bufs[sr.first_buf[c] + 2];
+      if (dsp.len > 0) sr.utf8_total[c] += sr.real_usize(b, dsp);
     }
-    out.cols[c].data = dalloc((uint64_t)(utf8_total[c] > 0 ? utf8_total[c] : 1));
-    out.cols[c].data_bytes = utf8_total[c];
+    out.cols[c].data = dalloc_elems(sr.utf8_total[c]);
+    out.cols[c].data_bytes = sr.utf8_total[c];
   }
+}
 
-  // decompress jobs: fixed data straight into columns; validity + utf8
-  // offsets into scratch (placed after with bitcopy / rebase)
-  struct Scratch { DBufPtr buf; };
-  std::vector<bg_lz4_frame> frames;
-  std::vector<int64_t> expect;
-  struct Fixup {
-    int kind;  // 0 validity bitcopy, 1 utf8 offsets place
-    size_t c;
-    DBufPtr scratch;
-    int64_t rows, row_cursor, data_cursor;
-  };
-  std::vector<Fixup> fixups;
-  std::vector<int64_t> row_cursor_per_batch(batches.size());
-  std::vector<int64_t> utf8_cursor(ncols, 0);
+// one source buffer -> dst: a copy when stored raw, else an LZ4 frame job
+static void schedule_buffer(ShuffleRead& sr, const BatchSrc& b,
+                            const bgipc::BufSpec& sp, uint8_t* dst,
+                            int64_t dst_cap) {
+  const uint8_t* src = sr.raw_dev->u8() + b.raw_base + sp.off;
+  if (!b.compressed) {
+    chk(bg_memcpy_dtod(dst, src, (uint64_t)sp.len), "bg_memcpy_dtod");
+  } else if (sr.usize_of(b, sp) == -1) {
+    // Arrow compressed-body convention: uncompressed-length prefix of -1
+    // marks a buffer stored raw (compression did not shrink)
+    chk(bg_memcpy_dtod(dst, src + 8, (uint64_t)(sp.len - 8)),
+        "bg_memcpy_dtod");
+  } else {
+    sr.frames.push_back({src + 8, dst, sp.len - 8, dst_cap});
+    sr.expect.push_back(sr.usize_of(b, sp));
+  }
+}
 
+// decompress jobs: fixed data straight into columns; validity + utf8
+// offsets into scratch (placed after with bitcopy / rebase)
+static std::vector<ShuffleFixup> schedule_buffers(ShuffleRead& sr,
+                                                  Table& out) {
+  std::vector<ShuffleFixup> fixups;
+  std::vector<int64_t> utf8_cursor(sr.dts.size(), 0);
   int64_t row_cursor = 0;
-  for (auto& b : batches) {
-    size_t bi = 0;
-    for (size_t c = 0; c < ncols; ++c) {
-      auto add_frame = [&](const bgipc::BufSpec& sp, uint8_t* dst,
-                           int64_t dst_cap) {
-        if (b.compressed) {
-          // Arrow compressed-body convention: uncompressed-length prefix
-          // of -1 marks a buffer stored raw (compression did not shrink)
-          if (usize_of(b, sp) == -1) {
-            chk(bg_memcpy_dtod(dst, raw_dev->u8() + b.raw_base + sp.off + 8,
-                               (uint64_t)(sp.len - 8)),
-                "bg_memcpy_dtod");
-            return;
-          }
-          frames.push_back({raw_dev->u8() + b.raw_base + sp.off + 8, dst,
-                            sp.len - 8, dst_cap});
-          expect.push_back(usize_of(b, sp));
-        } else {
-          chk(bg_memcpy_dtod(dst, raw_dev->u8() + b.raw_base + sp.off,
-                             (uint64_t)sp.len),
-              "bg_memcpy_dtod");
-        }
+  for (auto& b : sr.batches) {
+    for (size_t c = 0; c < sr.dts.size(); ++c) {
+      const size_t bi = sr.first_buf[c];
+      auto to_scratch = [&](const bgipc::BufSpec& sp, int kind) {
+        int64_t u = sr.real_usize(b, sp);
+        DBufPtr scr = dalloc((uint64_t)u + 8);
+        schedule_buffer(sr, b, sp, scr->u8(), u + 8);
+        fixups.push_back({kind, c, scr, b.rows, row_cursor, utf8_cursor[c]});
       };
-      const auto& vsp = b.bufs[bi];
-      if (vsp.len > 0) {
-        int64_t vu = real_usize(b, vsp);
-        DBufPtr scr = dalloc((uint64_t)vu + 8);
-        add_frame(vsp, scr->u8(), vu + 8);
-        fixups.push_back({0, c, scr, b.rows, row_cursor, 0});
-      }
-      if (dts[c].dt == BG_DT_UTF8) {
-        const auto& osp = b.bufs[bi + 1];
+      if (b.bufs[bi].len > 0) to_scratch(b.bufs[bi], 0);
+      if (sr.dts[c].dt == BG_DT_UTF8) {
+        to_scratch(b.bufs[bi + 1], 1);
         const auto& dsp = b.bufs[bi + 2];
-        int64_t ou = real_usize(b, osp);
-        DBufPtr oscr = dalloc((uint64_t)ou + 8);
-        add_frame(osp, oscr->u8(), ou + 8);
-        fixups.push_back({1, c, oscr, b.rows, row_cursor, utf8_cursor[c]});
         if (dsp.len > 0) {
-          int64_t du = real_usize(b, dsp);
-          add_frame(dsp, out.cols[c].data->u8() + utf8_cursor[c],
-                    utf8_total[c] - utf8_cursor[c] + 8);
+          int64_t du = sr.real_usize(b, dsp);
+          schedule_buffer(sr, b, dsp, out.cols[c].data->u8() + utf8_cursor[c],
+                          sr.utf8_total[c] - utf8_cursor[c] + 8);
           utf8_cursor[c] += du;
         }
-        bi += 3;
       } else {
-        const auto& dsp = b.bufs[bi + 1];
-        int64_t esz = dt_size(dts[c].dt);
-        add_frame(dsp, out.cols[c].data->u8() + row_cursor * esz,
-                  (total - row_cursor) * esz + 8);
-        bi += 2;
+        int64_t esz = dt_size(sr.dts[c].dt);
+        schedule_buffer(sr, b, b.bufs[bi + 1],
+                        out.cols[c].data->u8() + row_cursor * esz,
+                        (sr.total - row_cursor) * esz + 8);
       }
     }
     row_cursor += b.rows;
   }
+  return fixups;
+}
 
-  if (!frames.empty()) {
-    std::vector<int64_t> lens(frames.size());
-    chk(bg_lz4_decompress(frames.data(), (int64_t)frames.size(), lens.data()),
-        "bg_lz4_decompress");
-    for (size_t i = 0; i < frames.size(); ++i)
-      if (lens[i] != expect[i])
-        throw StageError(BG_ERR_INVALID, "shuffle read: LZ4 frame mismatch");
-  }
-
-  // place validity bits / utf8 offsets
+// place validity bits / utf8 offsets
+static void place_fixups(const std::vector<ShuffleFixup>& fixups, Table& out) {
   for (auto& fx : fixups) {
     if (fx.kind == 0) {
       chk(bg_bitcopy(fx.scratch->u8(), fx.rows, out.cols[fx.c].validity->u8(),
@@ -643,11 +629,224 @@ static Table read_shuffle_locations(const std::vector<Value*>& locations,
           "bg_sub_i32");
     }
   }
+}
+
+static Table read_shuffle_locations(const std::vector<Value*>& locations,
+                                    const std::vector<DtSpec>& dts,
+                                    const std::vector<std::string>& names) {
+  ShuffleRead sr(dts);
+  auto ranges = gather_ranges(locations, sr.all);
+  sr.batches = walk_batches(sr.all, ranges, dts.size());
+  for (auto& b : sr.batches) sr.total += b.rows;
+  // 2 buffers per column (validity, data), 3 for utf8 (+ offsets)
+  size_t nbufs = 0;
+  for (auto& d : dts) {
+    sr.first_buf.push_back(nbufs);
+    nbufs += d.dt == BG_DT_UTF8 ? 3 : 2;
+  }
+
+  Table out;
+  out.n = sr.total;
+  out.names = names;
+  if (sr.total == 0) {
+    for (auto& d : dts) {
+      Col col = make_col(d);
+      col.data = dalloc(16);
+      if (col.dtype == BG_DT_UTF8) {
+        col.offsets = dalloc(4);
+        chk(bg_memset(col.offsets->p, 0, 4), "bg_memset");
+      }
+      out.cols.push_back(std::move(col));
+    }
+    return out;
+  }
+
+  sr.raw_dev = upload(sr.all.data(), sr.all.size());
+  alloc_shuffle_columns(sr, out);
+  auto fixups = schedule_buffers(sr, out);
+  if (!sr.frames.empty()) {
+    std::vector<int64_t> lens(sr.frames.size());
+    chk(bg_lz4_decompress(sr.frames.data(), (int64_t)sr.frames.size(),
+                          lens.data()),
+        "bg_lz4_decompress");
+    for (size_t i = 0; i < sr.frames.size(); ++i)
+      if (lens[i] != sr.expect[i])
+        throw StageError(BG_ERR_INVALID, "shuffle read: LZ4 frame mismatch");
+  }
+  place_fixups(fixups, out);
   chk(bg_synchronize(), "bg_synchronize");
   return out;
 }
-
 #include "stage_parquet.h"
+
+struct PqPage {
+  int rg;
+  int type;  // 0 data, 2 dict
+  size_t data_pos;
+  int64_t csz, usz, nvals, ndict;
+  int enc;
+  int64_t soff;  // slot in the decompressed scratch
+};
+// a data page with its running value cursor
+struct PqDataPage {
+  int64_t soff, usz, dst_off, nvals;
+  int rg, enc;
+};
+
+// What the decode steps of one parquet column share.
+struct PqDecode {
+  int64_t src_esz = 0, dst_esz = 0;
+  bool is_flba = false;
+  int mode = 0;                // 2: OPTIONAL column (max_def 1), 0: REQUIRED
+  DBufPtr scratch;             // every page decompressed, at PqPage::soff
+  std::vector<PqDataPage> dp;  // data pages in file order
+  DBufPtr vidx, npres;         // OPTIONAL: value slot map, per-page presents
+
+  const uint32_t* vidx_at(size_t i) const {
+    return mode ? (const uint32_t*)(vidx->u8() + 4 * dp[i].dst_off) : nullptr;
+  }
+  const int64_t* npres_at(size_t i) const {
+    return mode ? (const int64_t*)(npres->u8() + 8 * i) : nullptr;
+  }
+};
+
+static std::vector<PqPage> pq_walk_pages(const uint8_t* h_file,
+                                         size_t file_len,
+                                         const PqColumnSpec& spec,
+                                         int64_t* scratch_total,
+                                         int64_t* total_values) {
+  std::vector<PqPage> pages;
+  for (size_t rg = 0; rg < spec.chunks.size(); ++rg) {
+    const PqChunk& ch = spec.chunks[rg];
+    size_t pos = (size_t)ch.start;
+    const size_t end = (size_t)(ch.start + ch.size);
+    *total_values += ch.num_values;
+    while (pos < end) {
+      PageHeader ph = parse_page_header(h_file, file_len, pos);
+      if (ph.type == 0 && ph.enc != 0 && ph.enc != 2 && ph.enc != 8)
+        throw StageError(BG_ERR_UNSUPPORTED,
+                         "parquet scan: encoding " + std::to_string(ph.enc) +
+                             " — use the Python reader (DELTA*/BSS)");
+      pages.push_back({(int)rg, ph.type, ph.data_pos, ph.csz, ph.usz,
+                       ph.nvals, ph.ndict, ph.enc, *scratch_total});
+      *scratch_total += (ph.usz + 255) & ~255LL;
+      pos = ph.data_pos + (size_t)ph.csz;
+    }
+  }
+  return pages;
+}
+
+// decompress (or copy) every page into its scratch slot
+static DBufPtr pq_decompress_pages(const std::vector<PqPage>& pages,
+                                   const DBufPtr& d_file, bool snappy,
+                                   int64_t scratch_total) {
+  DBufPtr scratch = dalloc((uint64_t)(scratch_total > 0 ? scratch_total : 256));
+  if (!snappy) {
+    for (auto& p : pages)
+      chk(bg_memcpy_dtod(scratch->u8() + p.soff, d_file->u8() + p.data_pos,
+                         (uint64_t)p.csz),
+          "bg_memcpy_dtod");
+    return scratch;
+  }
+  std::vector<bg_snappy_page> jobs;
+  for (auto& p : pages)
+    jobs.push_back({d_file->u8() + p.data_pos, scratch->u8() + p.soff, p.csz,
+                    p.usz + 8});
+  std::vector<int64_t> lens(jobs.size());
+  chk(bg_snappy_decompress(jobs.data(), (int64_t)jobs.size(), lens.data()),
+      "bg_snappy_decompress");
+  for (size_t i = 0; i < jobs.size(); ++i)
+    if (lens[i] != pages[i].usz)
+      throw StageError(BG_ERR_INVALID, "parquet scan: snappy page failed");
+  return scratch;
+}
+
+// OPTIONAL column: definition levels -> validity bitmap + slot map
+static void pq_def_levels(PqDecode& d, int64_t total_values, Col& out) {
+  const int64_t nwords = (total_values + 31) / 32;
+  out.validity = dalloc((uint64_t)std::max<int64_t>(nwords, 1) * 4 + 8);
+  chk(bg_memset(out.validity->p, 0, out.validity->bytes), "bg_memset");
+  d.vidx = dalloc_elems(total_values, 4);
+  d.npres = dalloc_elems((int64_t)d.dp.size(), 8);
+  std::vector<bg_def_levels_job> djobs;
+  for (size_t i = 0; i < d.dp.size(); ++i)
+    djobs.push_back({d.scratch->u8() + d.dp[i].soff,
+                     (uint32_t*)(d.vidx->u8() + 4 * d.dp[i].dst_off),
+                     (uint32_t*)out.validity->p, d.dp[i].usz, d.dp[i].nvals,
+                     d.dp[i].dst_off, (int64_t*)(d.npres->u8() + 8 * i)});
+  chk(bg_def_levels_batch(djobs.data(), (int64_t)djobs.size()),
+      "bg_def_levels_batch");
+}
+
+// PLAIN pages: one batched extract
+static void pq_extract_plain(const PqDecode& d, Col& out) {
+  std::vector<bg_page_extract_job> ejobs;
+  for (size_t i = 0; i < d.dp.size(); ++i) {
+    if (d.dp[i].enc != 0) continue;
+    ejobs.push_back({d.scratch->u8() + d.dp[i].soff,
+                     out.data->u8() + d.dp[i].dst_off * d.dst_esz,
+                     d.dp[i].usz, d.dp[i].nvals, d.src_esz, d.mode,
+                     d.is_flba ? 1 : 0, d.vidx_at(i), d.npres_at(i)});
+  }
+  if (!ejobs.empty())
+    chk(bg_page_extract_batch(ejobs.data(), (int64_t)ejobs.size()),
+        "bg_page_extract_batch");
+}
+
+// dictionary-coded pages: PLAIN-decode dictionaries, expand indices, gather
+static void pq_dict_gather(const PqDecode& d,
+                           const std::map<int, PqPage>& dict_of, Col& out) {
+  std::vector<size_t> dpg;
+  for (size_t i = 0; i < d.dp.size(); ++i)
+    if (d.dp[i].enc == 2 || d.dp[i].enc == 8) dpg.push_back(i);
+  if (dpg.empty()) return;
+  std::map<int, DBufPtr> dict_bufs;
+  std::vector<bg_page_extract_job> dj;
+  for (auto& kv : dict_of) {
+    const PqPage& dict = kv.second;
+    DBufPtr buf = dalloc_elems(dict.ndict, d.dst_esz);
+    dict_bufs[kv.first] = buf;
+    dj.push_back({d.scratch->u8() + dict.soff, buf->u8(), dict.usz,
+                  dict.ndict, d.src_esz, 0, d.is_flba ? 1 : 0, nullptr,
+                  nullptr});
+  }
+  if (!dj.empty())
+    chk(bg_page_extract_batch(dj.data(), (int64_t)dj.size()),
+        "bg_page_extract(dicts)");
+
+  int64_t nidx_total = 0;
+  for (size_t i : dpg) nidx_total += d.dp[i].nvals;
+  DBufPtr idx = dalloc_elems(nidx_total, 4);
+  DBufPtr dense;
+  if (d.mode) dense = dalloc_elems(nidx_total, 4);
+  std::vector<bg_dict_indices_job> ijobs;
+  struct Gather {
+    int rg;
+    int64_t ioff, dst_off, nvals;
+  };
+  std::vector<Gather> merged;  // adjacent pages of one rg gather as one
+  int64_t run = 0;
+  for (size_t i : dpg) {
+    const PqDataPage& p = d.dp[i];
+    ijobs.push_back({d.scratch->u8() + p.soff,
+                     (uint32_t*)(idx->u8() + 4 * run), p.usz, p.nvals, d.mode,
+                     0, d.vidx_at(i), d.npres_at(i),
+                     d.mode ? (uint32_t*)(dense->u8() + 4 * run) : nullptr});
+    if (!merged.empty() && merged.back().rg == p.rg &&
+        merged.back().dst_off + merged.back().nvals == p.dst_off)
+      merged.back().nvals += p.nvals;
+    else
+      merged.push_back({p.rg, run, p.dst_off, p.nvals});
+    run += p.nvals;
+  }
+  chk(bg_dict_indices_batch(ijobs.data(), (int64_t)ijobs.size()),
+      "bg_dict_indices_batch");
+  for (auto& gth : merged)
+    chk(bg_gather(dict_bufs[gth.rg]->p, d.dst_esz,
+                  (const uint32_t*)(idx->u8() + 4 * gth.ioff), gth.nvals,
+                  out.data->u8() + gth.dst_off * d.dst_esz),
+        "bg_gather(dict)");
+}
 
 // The device decode pipeline for one parquet column (subset: V1 pages,
 // PLAIN + RLE_DICTIONARY, INT32/INT64/DOUBLE/FLBA, max_def <= 1,
@@ -658,14 +857,14 @@ static Table read_shuffle_locations(const std::vector<Value*>& locations,
 Col parquet_read_column(const uint8_t* h_file, size_t file_len,
                         const DBufPtr& d_file, const PqColumnSpec& spec,
                         const DtSpec& out_dt) {
-  const bool is_flba = spec.phys == "FLBA";
-  int64_t src_esz, dst_esz;
-  if (spec.phys == "INT32") src_esz = dst_esz = 4;
+  PqDecode d;
+  d.is_flba = spec.phys == "FLBA";
+  if (spec.phys == "INT32") d.src_esz = d.dst_esz = 4;
   else if (spec.phys == "INT64" || spec.phys == "DOUBLE")
-    src_esz = dst_esz = 8;
-  else if (is_flba) {
-    src_esz = spec.flba_len;
-    dst_esz = 16;
+    d.src_esz = d.dst_esz = 8;
+  else if (d.is_flba) {
+    d.src_esz = spec.flba_len;
+    d.dst_esz = 16;
   } else {
     throw StageError(BG_ERR_UNSUPPORTED,
                      "parquet scan: physical type " + spec.phys +
@@ -677,181 +876,32 @@ Col parquet_read_column(const uint8_t* h_file, size_t file_len,
                      "parquet scan: codec " + spec.codec +
                          " — use the Python reader (ZSTD/GZIP bridge)");
 
-  struct Page {
-    int rg;
-    int type;  // 0 data, 2 dict
-    size_t data_pos;
-    int64_t csz, usz, nvals, ndict;
-    int enc;
-    int64_t soff;
-  };
-  std::vector<Page> pages;
   int64_t scratch_total = 0, total_values = 0;
-  for (size_t rg = 0; rg < spec.chunks.size(); ++rg) {
-    const PqChunk& ch = spec.chunks[rg];
-    size_t pos = (size_t)ch.start;
-    const size_t end = (size_t)(ch.start + ch.size);
-    total_values += ch.num_values;
-    while (pos < end) {
-      PageHeader ph = parse_page_header(h_file, file_len, pos);
-      if (ph.type == 0 && ph.enc != 0 && ph.enc != 2 && ph.enc != 8)
-        throw StageError(BG_ERR_UNSUPPORTED,
-                         "parquet scan: encoding " + std::to_string(ph.enc) +
-                             " — use the Python reader (DELTA*/BSS)");
-      Page p{(int)rg, ph.type, ph.data_pos, ph.csz, ph.usz, ph.nvals,
-             ph.ndict, ph.enc, scratch_total};
-      pages.push_back(p);
-      scratch_total += (ph.usz + 255) & ~255LL;
-      pos = ph.data_pos + (size_t)ph.csz;
-    }
-  }
-
-  DBufPtr scratch = dalloc((uint64_t)(scratch_total > 0 ? scratch_total : 256));
-  // decompress (or copy) every page into its scratch slot
-  if (snappy) {
-    std::vector<bg_snappy_page> jobs;
-    for (auto& p : pages)
-      jobs.push_back({d_file->u8() + p.data_pos, scratch->u8() + p.soff,
-                      p.csz, p.usz + 8});
-    std::vector<int64_t> lens(jobs.size());
-    chk(bg_snappy_decompress(jobs.data(), (int64_t)jobs.size(), lens.data()),
-        "bg_snappy_decompress");
-    for (size_t i = 0; i < jobs.size(); ++i)
-      if (lens[i] != pages[i].usz)
-        throw StageError(BG_ERR_INVALID, "parquet scan: snappy page failed");
-  } else {
-    for (auto& p : pages)
-      chk(bg_memcpy_dtod(scratch->u8() + p.soff, d_file->u8() + p.data_pos,
-                         (uint64_t)p.csz),
-          "bg_memcpy_dtod");
-  }
+  auto pages =
+      pq_walk_pages(h_file, file_len, spec, &scratch_total, &total_values);
+  d.scratch = pq_decompress_pages(pages, d_file, snappy, scratch_total);
 
   // data pages in file order with their running value cursor
-  struct DataPage {
-    int64_t soff, usz, dst_off, nvals;
-    int rg, enc;
-  };
-  std::vector<DataPage> dp;
   int64_t got = 0;
-  std::map<int, Page> dict_of;  // rg -> dictionary page
+  std::map<int, PqPage> dict_of;  // rg -> dictionary page
   for (auto& p : pages) {
     if (p.type == 2) dict_of[p.rg] = p;
     else if (p.type == 0) {
-      dp.push_back({p.soff, p.usz, got, p.nvals, p.rg, p.enc});
+      d.dp.push_back({p.soff, p.usz, got, p.nvals, p.rg, p.enc});
       got += p.nvals;
     }
   }
   if (got != total_values)
     throw StageError(BG_ERR_INVALID, "parquet scan: value count mismatch");
 
-  Col out;
-  out.dtype = out_dt.dt;
-  out.precision = out_dt.precision;
-  out.scale = out_dt.scale;
-  out.data = dalloc((uint64_t)(total_values > 0 ? total_values : 1) *
-                    (uint64_t)dst_esz);
-
-  // OPTIONAL column: definition levels -> validity bitmap + slot map
-  const int mode = spec.max_def > 0 ? 2 : 0;
-  DBufPtr vidx, npres;
-  if (mode) {
-    const int64_t nwords = (total_values + 31) / 32;
-    out.validity = dalloc((uint64_t)(nwords > 0 ? nwords : 1) * 4 + 8);
-    chk(bg_memset(out.validity->p, 0, out.validity->bytes), "bg_memset");
-    vidx = dalloc((uint64_t)(total_values > 0 ? total_values : 1) * 4);
-    npres = dalloc((uint64_t)(dp.size() ? dp.size() : 1) * 8);
-    std::vector<bg_def_levels_job> djobs;
-    for (size_t i = 0; i < dp.size(); ++i)
-      djobs.push_back({scratch->u8() + dp[i].soff,
-                       (uint32_t*)(vidx->u8() + 4 * dp[i].dst_off),
-                       (uint32_t*)out.validity->p, dp[i].usz, dp[i].nvals,
-                       dp[i].dst_off, (int64_t*)(npres->u8() + 8 * i)});
-    chk(bg_def_levels_batch(djobs.data(), (int64_t)djobs.size()),
-        "bg_def_levels_batch");
-  }
-
-  // PLAIN pages: one batched extract
-  std::vector<bg_page_extract_job> ejobs;
-  std::vector<size_t> eidx;
-  for (size_t i = 0; i < dp.size(); ++i) {
-    if (dp[i].enc != 0) continue;
-    ejobs.push_back({scratch->u8() + dp[i].soff,
-                     out.data->u8() + dp[i].dst_off * dst_esz, dp[i].usz,
-                     dp[i].nvals, src_esz, mode, is_flba ? 1 : 0,
-                     mode ? (const uint32_t*)(vidx->u8() + 4 * dp[i].dst_off)
-                          : nullptr,
-                     mode ? (const int64_t*)(npres->u8() + 8 * i) : nullptr});
-    eidx.push_back(i);
-  }
-  if (!ejobs.empty())
-    chk(bg_page_extract_batch(ejobs.data(), (int64_t)ejobs.size()),
-        "bg_page_extract_batch");
-
-  // dictionary-coded pages: PLAIN-decode dictionaries, expand indices,
-  // gather
-  std::vector<size_t> dpg;
-  for (size_t i = 0; i < dp.size(); ++i)
-    if (dp[i].enc == 2 || dp[i].enc == 8) dpg.push_back(i);
-  if (!dpg.empty()) {
-    std::map<int, DBufPtr> dict_bufs;
-    std::vector<bg_page_extract_job> dj;
-    std::vector<int> dj_rg;
-    for (auto& kv : dict_of) {
-      const Page& d = kv.second;
-      DBufPtr buf = dalloc((uint64_t)(d.ndict > 0 ? d.ndict : 1) *
-                           (uint64_t)dst_esz);
-      dict_bufs[kv.first] = buf;
-      dj.push_back({scratch->u8() + d.soff, buf->u8(), d.usz, d.ndict, src_esz,
-                    0, is_flba ? 1 : 0, nullptr, nullptr});
-      dj_rg.push_back(kv.first);
-    }
-    if (!dj.empty())
-      chk(bg_page_extract_batch(dj.data(), (int64_t)dj.size()),
-          "bg_page_extract(dicts)");
-
-    int64_t nidx_total = 0;
-    for (size_t i : dpg) nidx_total += dp[i].nvals;
-    DBufPtr idx = dalloc((uint64_t)(nidx_total > 0 ? nidx_total : 1) * 4);
-    DBufPtr dense;
-    if (mode) dense = dalloc((uint64_t)(nidx_total > 0 ? nidx_total : 1) * 4);
-    std::vector<bg_dict_indices_job> ijobs;
-    int64_t run = 0;
-    struct Gather {
-      int rg;
-      int64_t ioff, dst_off, nvals;
-    };
-    std::vector<Gather> gathers;
-    for (size_t i : dpg) {
-      ijobs.push_back({scratch->u8() + dp[i].soff,
-                       (uint32_t*)(idx->u8() + 4 * run), dp[i].usz,
-                       dp[i].nvals, mode, 0,
-                       mode ? (const uint32_t*)(vidx->u8() + 4 * dp[i].dst_off)
-                            : nullptr,
-                       mode ? (const int64_t*)(npres->u8() + 8 * i) : nullptr,
-                       mode ? (uint32_t*)(dense->u8() + 4 * run) : nullptr});
-      gathers.push_back({dp[i].rg, run, dp[i].dst_off, dp[i].nvals});
-      run += dp[i].nvals;
-    }
-    chk(bg_dict_indices_batch(ijobs.data(), (int64_t)ijobs.size()),
-        "bg_dict_indices_batch");
-    // merge adjacent pages of one rg into single gathers
-    std::vector<Gather> merged;
-    for (auto& gth : gathers) {
-      if (!merged.empty() && merged.back().rg == gth.rg &&
-          merged.back().dst_off + merged.back().nvals == gth.dst_off)
-        merged.back().nvals += gth.nvals;
-      else
-        merged.push_back(gth);
-    }
-    for (auto& gth : merged)
-      chk(bg_gather(dict_bufs[gth.rg]->p, dst_esz,
-                    (const uint32_t*)(idx->u8() + 4 * gth.ioff), gth.nvals,
-                    out.data->u8() + gth.dst_off * dst_esz),
-          "bg_gather(dict)");
-  }
+  Col out = make_col(out_dt);
+  out.data = dalloc_elems(total_values, d.dst_esz);
+  d.mode = spec.max_def > 0 ? 2 : 0;
+  if (d.mode) pq_def_levels(d, total_values, out);
+  pq_extract_plain(d, out);
+  pq_dict_gather(d, dict_of, out);
   return out;
 }
-
 // Read a "parquet" scan source: plan carries the footer-derived chunk
 // metadata per column (start/size/num_values, codec, physical type) —
 // hosts parse footers natively (pyarrow / parquet-rs); stage.py's
@@ -930,10 +980,7 @@ static Table scan(const Value& node) {
     if (files.size() != dts.size())
       throw StageError(BG_ERR_INVALID, "raw source: files != schema len");
     for (size_t c = 0; c < dts.size(); ++c) {
-      Col col;
-      col.dtype = dts[c].dt;
-      col.precision = dts[c].precision;
-      col.scale = dts[c].scale;
+      Col col = make_col(dts[c]);
       const Value& fv = *files[c];
       if (col.dtype == BG_DT_UTF8) {
         auto offs = read_file_range(fv.get_str("offsets"), 0, -1);
@@ -987,10 +1034,8 @@ static Col eval_dec_binary(const Table& t, int op_cc, int op_cl, int op_lc,
                            const Value& l, const Value& r) {
   ExprVal a = eval_expr(t, l);
   ExprVal b = eval_expr(t, r);
-  Col out;
-  out.dtype = BG_DT_DECIMAL128;
-  out.precision = 38;
-  out.data = dalloc((uint64_t)(t.n > 0 ? t.n : 1) * 16);
+  Col out = make_col({BG_DT_DECIMAL128, 38, 0});
+  out.data = dalloc_elems(t.n, 16);
   if (!a.is_lit && !b.is_lit) {
     out.scale = (op_cc == 0) ? a.col.scale + b.col.scale : a.col.scale;
     bg_column ba = to_bg(a.col, t.n), bb = to_bg(b.col, t.n);
@@ -1023,9 +1068,9 @@ static Col eval_dec_binary(const Table& t, int op_cc, int op_cl, int op_lc,
       if (!out.validity) {
         out.validity = s->validity ? s->validity : nullptr;
         if (!out.validity) {  // external bitmap: copy it
-          uint64_t vb = (uint64_t)((t.n + 63) / 64) * 8 + 8;
-          out.validity = dalloc(vb);
-          chk(bg_memcpy_dtod(out.validity->p, s->vptr(), vb),
+          out.validity = alloc_bitmap(t.n);
+          chk(bg_memcpy_dtod(out.validity->p, s->vptr(),
+                             out.validity->bytes),
               "bg_memcpy_dtod");
         }
       }
@@ -1038,7 +1083,7 @@ static Col eval_dec_binary(const Table& t, int op_cc, int op_cl, int op_lc,
 static ExprVal eval_expr(const Table& t, const Value& e) {
   ExprVal v;
   if (e.has("col")) {
-    v.col = t.cols[(size_t)t.idx(e.get_str("col"))];
+    v.col = t.col(e.get_str("col"));
     return v;
   }
   if (e.has("lit")) {
@@ -1070,11 +1115,8 @@ static ExprVal eval_expr(const Table& t, const Value& e) {
         if (a.is_lit) throw StageError(BG_ERR_INVALID, "sub of two literals");
         __int128 litv = ((__int128)b.lit_hi << 64) | (uint64_t)b.lit_lo;
         litv = -litv;
-        Col out;
-        out.dtype = BG_DT_DECIMAL128;
-        out.precision = 38;
-        out.scale = a.col.scale;
-        out.data = dalloc((uint64_t)(t.n > 0 ? t.n : 1) * 16);
+        Col out = make_col({BG_DT_DECIMAL128, 38, a.col.scale});
+        out.data = dalloc_elems(t.n, 16);
         bg_column ba = to_bg(a.col, t.n);
         chk(bg_project_dec128(5, &ba, nullptr, (int64_t)(uint64_t)litv,
                               (int64_t)(uint64_t)((unsigned __int128)litv >> 64),
@@ -1103,12 +1145,10 @@ static ExprVal eval_expr(const Table& t, const Value& e) {
     // materialise literal branches as constant columns
     auto materialise = [&](ExprVal& ev, const ExprVal& other) -> Col {
       if (!ev.is_lit) return ev.col;
-      Col out;
-      out.dtype = other.is_lit ? BG_DT_DECIMAL128 : other.col.dtype;
-      out.precision = other.is_lit ? 38 : other.col.precision;
-      out.scale = other.is_lit ? 0 : other.col.scale;
+      Col out = make_col(other.is_lit ? DtSpec{BG_DT_DECIMAL128, 38, 0}
+                                      : other.col.spec());
       int64_t esz = dt_size(out.dtype);
-      out.data = dalloc((uint64_t)(t.n > 0 ? t.n : 1) * (uint64_t)esz);
+      out.data = dalloc_elems(t.n, esz);
       chk(bg_fill_const(out.data->p, t.n, esz, ev.lit_lo, ev.lit_hi),
           "bg_fill_const");
       return out;
@@ -1122,7 +1162,7 @@ static ExprVal eval_expr(const Table& t, const Value& e) {
     v2.col.precision = ca.precision ? ca.precision : cb.precision;
     v2.col.scale = ca.scale ? ca.scale : cb.scale;
     int64_t esz = dt_size(ca.dtype);
-    v2.col.data = dalloc((uint64_t)(t.n > 0 ? t.n : 1) * (uint64_t)esz);
+    v2.col.data = dalloc_elems(t.n, esz);
     chk(bg_select(mask->u8(), ca.dptr(), cb.dptr(), esz, t.n,
                   v2.col.data->p),
         "bg_select");
@@ -1229,11 +1269,8 @@ static void eval_exprs_fused(const Table& t,
     for (int ci : p.col_ids) cols.push_back(to_bg(t.cols[(size_t)ci], t.n));
     std::vector<void*> douts;
     for (size_t fi = 0; fi < fused.size(); ++fi) {
-      Col c;
-      c.dtype = BG_DT_DECIMAL128;
-      c.precision = 38;
-      c.scale = scales[fi];
-      c.data = dalloc((uint64_t)(t.n > 0 ? t.n : 1) * 16);
+      Col c = make_col({BG_DT_DECIMAL128, 38, scales[fi]});
+      c.data = dalloc_elems(t.n, 16);
       douts.push_back(c.data->p);
       (*outs)[fused[fi]] = std::move(c);
     }
@@ -1297,14 +1334,11 @@ static DBufPtr eval_filter_mask(const Table& t, const Value& node) {
     if (p->has("hi")) parse_i128(p->at("hi"), &q.hi_lo, &q.hi_hi);
     bp.push_back(q);
   }
-  DBufPtr mask = dalloc((uint64_t)((t.n + 63) / 64) * 8 + 8);
-  if (!bp.empty()) {
+  DBufPtr mask = alloc_bitmap(t.n, bp.empty() ? 0xFF : -1);
+  if (!bp.empty())
     chk(bg_eval_predicates(cols.data(), (int32_t)cols.size(), bp.data(),
                            (int32_t)bp.size(), t.n, mask->u8()),
         "bg_eval_predicates");
-  } else {
-    chk(bg_memset(mask->p, 0xFF, mask->bytes), "bg_memset");
-  }
   for (auto* ip : ins) {
     std::vector<int64_t> vals;
     for (auto& v : ip->get_arr("in")) {
@@ -1312,7 +1346,7 @@ static DBufPtr eval_filter_mask(const Table& t, const Value& node) {
       parse_i128(*v, &lo, &hi);
       vals.push_back(lo);
     }
-    bg_column c = to_bg(t.cols[(size_t)t.idx(ip->get_str("col"))], t.n);
+    bg_column c = to_bg(t.col(ip->get_str("col")), t.n);
     chk(bg_eval_in(&c, vals.data(), (int32_t)vals.size(), t.n, mask->u8()),
         "bg_eval_in");
   }
@@ -1343,7 +1377,7 @@ static DBufPtr eval_filter_mask(const Table& t, const Value& node) {
       terms.push_back(f.c_str());
       lens.push_back((int32_t)f.size());
     }
-    bg_column c = to_bg(t.cols[(size_t)t.idx(lp->get_str("col"))], t.n);
+    bg_column c = to_bg(t.col(lp->get_str("col")), t.n);
     chk(bg_eval_like(&c, terms.data(), lens.data(), (int32_t)terms.size(),
                      anchor_prefix ? 1 : 0, anchor_suffix ? 1 : 0,
                      lp->get_bool_or("negate", false) ? 1 : 0, t.n,
@@ -1376,7 +1410,7 @@ static DBufPtr eval_filter_node(const Table& t, const Value& node) {
 }
 
 static Table filter_materialize(const Table& t, DBufPtr mask) {
-  DBufPtr idx = dalloc((uint64_t)(t.n > 0 ? t.n : 1) * 4);
+  DBufPtr idx = dalloc_elems(t.n, 4);
   int64_t m = 0;
   chk(bg_mask_to_indices(mask->u8(), t.n, (uint32_t*)idx->p, &m),
       "bg_mask_to_indices");
@@ -1414,8 +1448,34 @@ static Table exec_project(const Value& node, Metrics& m) {
   return out;
 }
 
-// semi_build / anti_build emit build rows only (execution and
-// bg_stage_validate both check)
+// The join types of the plan grammar: the one list that bg_stage_validate
+// and execution both read.
+struct JoinKind {
+  const char* name;
+  int32_t type;
+  bool build_rows_only;  // emits build rows only, each at most once
+  bool probe_null_idx;   // unmatched probe rows carry BG_JOIN_NULL_IDX
+  bool build_tail;       // unmatched build rows follow the last chunk
+};
+static const JoinKind JOIN_KINDS[] = {
+    {"inner", BG_JOIN_INNER, false, false, false},
+    {"semi", BG_JOIN_SEMI, false, false, false},
+    {"anti", BG_JOIN_ANTI, false, false, false},
+    {"left", BG_JOIN_OUTER_PROBE, false, true, false},  // probe preserved
+    // build preserved (DataFusion LeftSemi / LeftAnti / Left / Full)
+    {"semi_build", BG_JOIN_SEMI_BUILD, true, false, false},
+    {"anti_build", BG_JOIN_ANTI_BUILD, true, false, false},
+    {"outer_build", BG_JOIN_OUTER_BUILD, false, false, true},
+    {"full", BG_JOIN_OUTER_FULL, false, true, true},
+};
+
+static const JoinKind& join_kind(const Value& node) {
+  const std::string jt = node.get_str_or("join_type", "inner");
+  for (auto& k : JOIN_KINDS)
+    if (jt == k.name) return k;
+  throw StageError(BG_ERR_UNSUPPORTED, "hash_join: join_type " + jt);
+}
+
 static void require_build_side(const std::string& jt, const Value& o) {
   if (o.get_str("side") != "build")
     throw StageError(BG_ERR_INVALID,
@@ -1423,54 +1483,204 @@ static void require_build_side(const std::string& jt, const Value& o) {
                          o.get_str("col") + "' is not side 'build'");
 }
 
+struct JoinOut {
+  bool build;  // taken from the build side (else the probe side)
+  std::string col, as;
+};
+
+// One entry of a join node's "output" list, checked against the join type.
+static JoinOut join_output(const JoinKind& k, const Value& o) {
+  if (k.build_rows_only) require_build_side(k.name, o);
+  const bool build = o.get_str("side") == "build";
+  const std::string col = o.get_str("col");
+  return {build, col, o.get_str_or("as", col)};
+}
+
+// The hash table of one join: the single-INT64-key inner join has a
+// specialised table, every other shape goes through the general one.
+struct JoinHandle {
+  void* h = nullptr;
+  const bool fast;
+  const int32_t type;
+  JoinHandle(const JoinHandle&) = delete;
+  JoinHandle& operator=(const JoinHandle&) = delete;
+  JoinHandle(const std::vector<bg_column>& bk, int64_t n, int32_t join_type)
+      : fast(bk.size() == 1 && bk[0].dtype == BG_DT_INT64 &&
+             join_type == BG_JOIN_INNER),
+        type(join_type) {
+    if (fast) chk(bg_hashjoin_build(&bk[0], n, &h), "bg_hashjoin_build");
+    else
+      chk(bg_hashjoin_build2(bk.data(), (int32_t)bk.size(), n, &h),
+          "bg_hashjoin_build2");
+  }
+  ~JoinHandle() {
+    if (h) (void)(fast ? bg_hashjoin_free(h) : bg_hashjoin_free2(h));
+  }
+  int64_t count(const std::vector<bg_column>& pk, int64_t len) {
+    int64_t matches = 0;
+    if (fast)
+      chk(bg_hashjoin_probe_count(h, &pk[0], len, &matches),
+          "bg_hashjoin_probe_count");
+    else
+      chk(bg_hashjoin_probe_count2(h, pk.data(), (int32_t)pk.size(), len,
+                                   type, &matches),
+          "bg_hashjoin_probe_count2");
+    return matches;
+  }
+  void fill(const std::vector<bg_column>& pk, int64_t len, uint32_t* pidx,
+            uint32_t* bidx) {
+    if (fast)
+      chk(bg_hashjoin_probe_fill(h, &pk[0], len, pidx, bidx),
+          "bg_hashjoin_probe_fill");
+    else
+      chk(bg_hashjoin_probe_fill2(h, pk.data(), (int32_t)pk.size(), len, type,
+                                  pidx, bidx),
+          "bg_hashjoin_probe_fill2");
+  }
+  // the build-rows calls exist for the general table only; the types that
+  // use them never take the fast path
+  void mark(const std::vector<bg_column>& pk, int64_t len) {
+    chk(bg_hashjoin_probe_mark2(h, pk.data(), (int32_t)pk.size(), len),
+        "bg_hashjoin_probe_mark2");
+  }
+  // build rows some probe row matched (matched=1) or none did (0), in
+  // ascending build order
+  int64_t build_rows(int matched, uint32_t* idx) {
+    int64_t rows = 0;
+    chk(bg_hashjoin_build_rows2(h, matched, &rows, idx),
+        "bg_hashjoin_build_rows2");
+    return rows;
+  }
+};
+
+// The two evaluated sides of a join with its key and output columns.
+struct JoinSides {
+  Table build, probe;
+  std::vector<int> pk_ids;  // probe key columns
+  std::vector<JoinOut> outs;
+
+  // probe key columns of the slice [start, start+len); the Cols own nothing
+  // new but must outlive the bg_column views taken of them
+  void slice_probe_keys(int64_t start, int64_t len, std::vector<Col>& sliced,
+                        std::vector<bg_column>& views) const {
+    for (int id : pk_ids) {
+      sliced.push_back(slice_col(probe.cols[(size_t)id], start, len));
+      views.push_back(to_bg(sliced.back(), len));
+    }
+  }
+  Col gather_build(const std::string& col, const DBufPtr& idx,
+                   int64_t rows) const {
+    return gather_col(build.col(col), build.n, (const uint32_t*)idx->p, rows);
+  }
+};
+
+// semi_build / anti_build: only the visited bitmap matters: mark per probe
+// chunk (no pair buffers), then list the build rows once, in ascending
+// build order
+static Table join_build_rows_only(JoinHandle& jh, const JoinSides& s,
+                                  int64_t chunk) {
+  for (int64_t start = 0; start < s.probe.n; start += chunk) {
+    const int64_t len = std::min(s.probe.n - start, chunk);
+    std::vector<bg_column> pk;
+    std::vector<Col> pk_sliced;
+    s.slice_probe_keys(start, len, pk_sliced, pk);
+    jh.mark(pk, len);
+  }
+  DBufPtr idx = dalloc_elems(s.build.n, 4);
+  Table out;
+  out.n = jh.build_rows(jh.type == BG_JOIN_SEMI_BUILD ? 1 : 0,
+                        (uint32_t*)idx->p);
+  for (auto& o : s.outs) {
+    out.names.push_back(o.as);
+    out.cols.push_back(s.gather_build(o.col, idx, out.n));
+  }
+  return out;
+}
+
+// One probe slice [start, start+len): count, fill, split the NULL-index
+// sentinels off, gather one piece per output.  Returns the pair count.
+static int64_t join_probe_chunk(JoinHandle& jh, const JoinKind& k,
+                                const JoinSides& s, int64_t start, int64_t len,
+                                std::vector<std::vector<Col>>& pieces) {
+  std::vector<bg_column> pk;
+  std::vector<Col> pk_sliced;
+  s.slice_probe_keys(start, len, pk_sliced, pk);
+  const int64_t matches = jh.count(pk, len);
+  DBufPtr pidx = dalloc_elems(matches, 4);
+  DBufPtr bidx = dalloc_elems(matches, 4);
+  jh.fill(pk, len, (uint32_t*)pidx->p, (uint32_t*)bidx->p);
+
+  DBufPtr bidx_clamped, outer_valid;
+  if (k.probe_null_idx) {
+    bidx_clamped = dalloc_elems(matches, 4);
+    outer_valid = alloc_bitmap(matches, 0xFF);
+    chk(bg_idx_sentinel((const uint32_t*)bidx->p, matches,
+                        (uint32_t*)bidx_clamped->p, outer_valid->u8()),
+        "bg_idx_sentinel");
+  }
+
+  for (size_t oi = 0; oi < s.outs.size(); ++oi) {
+    const JoinOut& o = s.outs[oi];
+    const bool outer_build = o.build && k.probe_null_idx;
+    Col c;
+    if (outer_build && k.type == BG_JOIN_OUTER_FULL && s.build.n == 0) {
+      // full join over an empty build side: every pair is an unmatched
+      // probe row, and there is no build row 0 to gather a filler from
+      c = null_col(s.build.col(o.col), matches);
+    } else if (o.build) {
+      c = s.gather_build(o.col, outer_build ? bidx_clamped : bidx, matches);
+      if (outer_build && c.validity) {
+        DBufPtr comb = alloc_bitmap(matches);
+        chk(bg_bitmap_and(c.validity->u8(), outer_valid->u8(), matches,
+                          comb->u8()),
+            "bg_bitmap_and");
+        c.validity = comb;
+      } else if (outer_build) {
+        c.validity = outer_valid;
+      }
+    } else {
+      // probe indices are chunk-relative: gather from the SLICE
+      Col ps = slice_col(s.probe.col(o.col), start, len);
+      c = gather_col(ps, len, (const uint32_t*)pidx->p, matches);
+    }
+    pieces[oi].push_back(std::move(c));
+  }
+  return matches;
+}
+
+// outer_build / full: one tail piece after the last chunk: the build rows
+// no probe row matched, with NULL probe-side columns.  Returns its rows.
+static int64_t join_unmatched_build_tail(JoinHandle& jh, const JoinSides& s,
+                                         std::vector<std::vector<Col>>& pieces) {
+  DBufPtr idx = dalloc_elems(s.build.n, 4);
+  const int64_t rows = jh.build_rows(0, (uint32_t*)idx->p);
+  for (size_t oi = 0; oi < s.outs.size(); ++oi) {
+    const JoinOut& o = s.outs[oi];
+    pieces[oi].push_back(o.build ? s.gather_build(o.col, idx, rows)
+                                 : null_col(s.probe.col(o.col), rows));
+  }
+  return rows;
+}
+
 static Table exec_join(const Value& node, Metrics& m) {
-  Table build = exec_plan(node.at("build"), m);
-  Table probe = exec_plan(node.at("probe"), m);
+  JoinSides s;
+  s.build = exec_plan(node.at("build"), m);
+  s.probe = exec_plan(node.at("probe"), m);
   auto& bkeys = node.get_arr("build_keys");
   auto& pkeys = node.get_arr("probe_keys");
   if (bkeys.size() != pkeys.size() || bkeys.empty() || bkeys.size() > 4)
     throw StageError(BG_ERR_INVALID, "hash_join: 1-4 matching key columns");
-  const std::string jt = node.get_str_or("join_type", "inner");
-  int32_t join_type;
-  if (jt == "inner") join_type = BG_JOIN_INNER;
-  else if (jt == "semi") join_type = BG_JOIN_SEMI;
-  else if (jt == "anti") join_type = BG_JOIN_ANTI;
-  else if (jt == "left") join_type = BG_JOIN_OUTER_PROBE;  // probe preserved
-  // build preserved (DataFusion LeftSemi / LeftAnti / Left / Full)
-  else if (jt == "semi_build") join_type = BG_JOIN_SEMI_BUILD;
-  else if (jt == "anti_build") join_type = BG_JOIN_ANTI_BUILD;
-  else if (jt == "outer_build") join_type = BG_JOIN_OUTER_BUILD;
-  else if (jt == "full") join_type = BG_JOIN_OUTER_FULL;
-  else
-    throw StageError(BG_ERR_UNSUPPORTED, "hash_join: join_type " + jt);
+  const JoinKind& k = join_kind(node);
 
   std::vector<bg_column> bk;
-  std::vector<int> pk_ids;
   for (size_t i = 0; i < bkeys.size(); ++i) {
-    bk.push_back(to_bg(build.cols[(size_t)build.idx(bkeys[i]->s)], build.n));
-    pk_ids.push_back(probe.idx(pkeys[i]->s));
-    if (bk[i].dtype != probe.cols[(size_t)pk_ids[i]].dtype)
+    bk.push_back(to_bg(s.build.col(bkeys[i]->s), s.build.n));
+    s.pk_ids.push_back(s.probe.idx(pkeys[i]->s));
+    if (bk[i].dtype != s.probe.cols[(size_t)s.pk_ids[i]].dtype)
       throw StageError(BG_ERR_INVALID, "hash_join: key dtype mismatch");
   }
-  const bool fast_int64 = bk.size() == 1 && bk[0].dtype == BG_DT_INT64 &&
-                          join_type == BG_JOIN_INNER;
-
-  struct HandleGuard {
-    void* h = nullptr;
-    bool fast = false;
-    ~HandleGuard() {
-      if (h) {
-        if (fast) (void)bg_hashjoin_free(h);
-        else (void)bg_hashjoin_free2(h);
-      }
-    }
-  } guard;
-  guard.fast = fast_int64;
-  if (fast_int64)
-    chk(bg_hashjoin_build(&bk[0], build.n, &guard.h), "bg_hashjoin_build");
-  else
-    chk(bg_hashjoin_build2(bk.data(), (int32_t)bk.size(), build.n, &guard.h),
-        "bg_hashjoin_build2");
+  for (auto& o : node.get_arr("output")) s.outs.push_back(join_output(k, *o));
+  JoinHandle jh(bk, s.build.n, k.type);
 
   // Memory-pressure bound (the spill analogue of sort_shuffle/writer.rs:
   // 650-686 for join temporaries): probe in slices of probe_chunk_rows
@@ -1478,160 +1688,23 @@ static Table exec_join(const Value& node, Metrics& m) {
   // probe side's size; chunk outputs are concatenated afterwards.  0 =
   // unchunked.  Slices start at 64-row multiples (validity byte-aligned).
   int64_t chunk = node.get_int_or("probe_chunk_rows", 0);
-  if (chunk <= 0 || chunk >= probe.n) chunk = probe.n > 0 ? probe.n : 1;
+  if (chunk <= 0 || chunk >= s.probe.n) chunk = s.probe.n > 0 ? s.probe.n : 1;
   chunk = (chunk + 63) & ~63LL;
+  if (k.build_rows_only) return join_build_rows_only(jh, s, chunk);
 
-  // probe key columns of the slice [start, start+len); the Cols own nothing
-  // new but must outlive the bg_column views taken of them
-  auto slice_probe_keys = [&](int64_t start, int64_t len,
-                              std::vector<Col>& sliced,
-                              std::vector<bg_column>& views) {
-    for (int id : pk_ids) {
-      sliced.push_back(slice_col(probe.cols[(size_t)id], start, len));
-      views.push_back(to_bg(sliced.back(), len));
-    }
-  };
-
-  auto& outputs = node.get_arr("output");
-  std::vector<std::vector<Col>> pieces(outputs.size());
+  std::vector<std::vector<Col>> pieces(s.outs.size());
   std::vector<int64_t> piece_lens;
-  int64_t total_matches = 0;
-
-  if (join_type == BG_JOIN_SEMI_BUILD || join_type == BG_JOIN_ANTI_BUILD) {
-    // only the visited bitmap matters: mark per probe chunk (no pair
-    // buffers), then list the build rows once, in ascending build order
-    for (auto& o : outputs) require_build_side(jt, *o);
-    for (int64_t start = 0; start < probe.n; start += chunk) {
-      const int64_t len = probe.n - start < chunk ? probe.n - start : chunk;
-      std::vector<bg_column> pk;
-      std::vector<Col> pk_sliced;
-      slice_probe_keys(start, len, pk_sliced, pk);
-      chk(bg_hashjoin_probe_mark2(guard.h, pk.data(), (int32_t)pk.size(),
-                                  len),
-          "bg_hashjoin_probe_mark2");
-    }
-    DBufPtr idx = dalloc((uint64_t)(build.n > 0 ? build.n : 1) * 4);
-    int64_t rows = 0;
-    chk(bg_hashjoin_build_rows2(guard.h,
-                                join_type == BG_JOIN_SEMI_BUILD ? 1 : 0,
-                                &rows, (uint32_t*)idx->p),
-        "bg_hashjoin_build_rows2");
-    Table out;
-    out.n = rows;
-    for (auto& o : outputs) {
-      const std::string col = o->get_str("col");
-      out.names.push_back(o->get_str_or("as", col));
-      out.cols.push_back(gather_col(build.cols[(size_t)build.idx(col)],
-                                    build.n, (const uint32_t*)idx->p, rows));
-    }
-    return out;
-  }
-  // the types whose unmatched probe rows carry BG_JOIN_NULL_IDX build ids
-  const bool probe_outer =
-      join_type == BG_JOIN_OUTER_PROBE || join_type == BG_JOIN_OUTER_FULL;
-
-  for (int64_t start = 0; start < probe.n || (probe.n == 0 && start == 0);
-       start += chunk) {
-    const int64_t len =
-        probe.n - start < chunk ? probe.n - start : chunk;
-    std::vector<bg_column> pk;
-    std::vector<Col> pk_sliced;
-    slice_probe_keys(start, len, pk_sliced, pk);
-    int64_t matches = 0;
-    if (fast_int64)
-      chk(bg_hashjoin_probe_count(guard.h, &pk[0], len, &matches),
-          "bg_hashjoin_probe_count");
-    else
-      chk(bg_hashjoin_probe_count2(guard.h, pk.data(), (int32_t)pk.size(),
-                                   len, join_type, &matches),
-          "bg_hashjoin_probe_count2");
-    DBufPtr pidx = dalloc((uint64_t)(matches > 0 ? matches : 1) * 4);
-    DBufPtr bidx = dalloc((uint64_t)(matches > 0 ? matches : 1) * 4);
-    if (fast_int64)
-      chk(bg_hashjoin_probe_fill(guard.h, &pk[0], len, (uint32_t*)pidx->p,
-                                 (uint32_t*)bidx->p),
-          "bg_hashjoin_probe_fill");
-    else
-      chk(bg_hashjoin_probe_fill2(guard.h, pk.data(), (int32_t)pk.size(),
-                                  len, join_type, (uint32_t*)pidx->p,
-                                  (uint32_t*)bidx->p),
-          "bg_hashjoin_probe_fill2");
-
-    DBufPtr bidx_clamped, outer_valid;
-    if (probe_outer) {
-      bidx_clamped = dalloc((uint64_t)(matches > 0 ? matches : 1) * 4);
-      outer_valid = dalloc((uint64_t)((matches + 63) / 64) * 8 + 8);
-      chk(bg_memset(outer_valid->p, 0xFF, outer_valid->bytes), "bg_memset");
-      chk(bg_idx_sentinel((const uint32_t*)bidx->p, matches,
-                          (uint32_t*)bidx_clamped->p, outer_valid->u8()),
-          "bg_idx_sentinel");
-    }
-
-    for (size_t oi = 0; oi < outputs.size(); ++oi) {
-      const Value& o = *outputs[oi];
-      const std::string side = o.get_str("side");
-      const std::string col = o.get_str("col");
-      const bool outer_build = side == "build" && probe_outer;
-      Col c;
-      if (outer_build && join_type == BG_JOIN_OUTER_FULL && build.n == 0) {
-        // full join over an empty build side: every pair is an unmatched
-        // probe row, and there is no build row 0 to gather a filler from
-        c = null_col(build.cols[(size_t)build.idx(col)], matches);
-      } else if (side == "build") {
-        const uint32_t* idx =
-            (const uint32_t*)(outer_build ? bidx_clamped->p : bidx->p);
-        c = gather_col(build.cols[(size_t)build.idx(col)], build.n, idx,
-                       matches);
-        if (outer_build) {
-          if (c.validity) {
-            DBufPtr comb = dalloc((uint64_t)((matches + 63) / 64) * 8 + 8);
-            chk(bg_bitmap_and(c.validity->u8(), outer_valid->u8(), matches,
-                              comb->u8()),
-                "bg_bitmap_and");
-            c.validity = comb;
-          } else {
-            c.validity = outer_valid;
-          }
-        }
-      } else {
-        // probe indices are chunk-relative: gather from the SLICE
-        Col ps = slice_col(probe.cols[(size_t)probe.idx(col)], start, len);
-        c = gather_col(ps, len, (const uint32_t*)pidx->p, matches);
-      }
-      pieces[oi].push_back(std::move(c));
-    }
-    piece_lens.push_back(matches);
-    total_matches += matches;
-    if (probe.n == 0) break;
-  }
-
-  if (join_type == BG_JOIN_OUTER_BUILD || join_type == BG_JOIN_OUTER_FULL) {
-    // one tail piece after the last chunk: the build rows no probe row
-    // matched, with NULL probe-side columns
-    DBufPtr idx = dalloc((uint64_t)(build.n > 0 ? build.n : 1) * 4);
-    int64_t rows = 0;
-    chk(bg_hashjoin_build_rows2(guard.h, 0, &rows, (uint32_t*)idx->p),
-        "bg_hashjoin_build_rows2");
-    for (size_t oi = 0; oi < outputs.size(); ++oi) {
-      const Value& o = *outputs[oi];
-      const std::string col = o.get_str("col");
-      if (o.get_str("side") == "build")
-        pieces[oi].push_back(gather_col(build.cols[(size_t)build.idx(col)],
-                                        build.n, (const uint32_t*)idx->p,
-                                        rows));
-      else
-        pieces[oi].push_back(
-            null_col(probe.cols[(size_t)probe.idx(col)], rows));
-    }
-    piece_lens.push_back(rows);
-    total_matches += rows;
-  }
+  // an empty probe side still runs one (empty) slice
+  for (int64_t start = 0; start == 0 || start < s.probe.n; start += chunk)
+    piece_lens.push_back(join_probe_chunk(
+        jh, k, s, start, std::min(s.probe.n - start, chunk), pieces));
+  if (k.build_tail)
+    piece_lens.push_back(join_unmatched_build_tail(jh, s, pieces));
 
   Table out;
-  out.n = total_matches;
-  for (size_t oi = 0; oi < outputs.size(); ++oi) {
-    const Value& o = *outputs[oi];
-    out.names.push_back(o.get_str_or("as", o.get_str("col")));
+  for (int64_t len : piece_lens) out.n += len;
+  for (size_t oi = 0; oi < s.outs.size(); ++oi) {
+    out.names.push_back(s.outs[oi].as);
     if (pieces[oi].size() == 1)
       out.cols.push_back(std::move(pieces[oi][0]));
     else
@@ -1639,7 +1712,6 @@ static Table exec_join(const Value& node, Metrics& m) {
   }
   return out;
 }
-
 // q6-shape fusion: aggregate(no groups, sum(mul(dec,dec)) [+count]) over
 // filter(ge_lt date32, between dec128, lt dec128) over scan — the exact
 // Filter+Partial-Aggregate stage of approved/q6.txt, one fused kernel.
@@ -1670,14 +1742,11 @@ static bool try_q6_fusion(const Value& agg_node, Metrics& m, Table* out) {
   Table t = scan(scan_node);
   const Value *p_date = nullptr, *p_disc = nullptr, *p_qty = nullptr;
   for (auto& p : preds) {
-    int ci = t.idx(p->get_str("col"));
+    const int32_t dt = t.col(p->get_str("col")).dtype;
     const std::string cmp = p->get_str("cmp");
-    if (cmp == "ge_lt" && t.cols[(size_t)ci].dtype == BG_DT_DATE32)
-      p_date = p.get();
-    else if (cmp == "between" && t.cols[(size_t)ci].dtype == BG_DT_DECIMAL128)
-      p_disc = p.get();
-    else if (cmp == "lt" && t.cols[(size_t)ci].dtype == BG_DT_DECIMAL128)
-      p_qty = p.get();
+    if (cmp == "ge_lt" && dt == BG_DT_DATE32) p_date = p.get();
+    else if (cmp == "between" && dt == BG_DT_DECIMAL128) p_disc = p.get();
+    else if (cmp == "lt" && dt == BG_DT_DECIMAL128) p_qty = p.get();
   }
   if (!p_date || !p_disc || !p_qty) return false;
   // the sum multiplies discount by the price column
@@ -1688,10 +1757,10 @@ static bool try_q6_fusion(const Value& agg_node, Metrics& m, Table* out) {
     price_name = mops[0]->get_str("col");
   else return false;
 
-  bg_column sd = to_bg(t.cols[(size_t)t.idx(p_date->get_str("col"))], t.n);
-  bg_column cd = to_bg(t.cols[(size_t)t.idx(disc_name)], t.n);
-  bg_column cq = to_bg(t.cols[(size_t)t.idx(p_qty->get_str("col"))], t.n);
-  bg_column cp = to_bg(t.cols[(size_t)t.idx(price_name)], t.n);
+  bg_column sd = to_bg(t.col(p_date->get_str("col")), t.n);
+  bg_column cd = to_bg(t.col(disc_name), t.n);
+  bg_column cq = to_bg(t.col(p_qty->get_str("col")), t.n);
+  bg_column cp = to_bg(t.col(price_name), t.n);
   int64_t dlo_lo, dlo_hi, dhi_lo, dhi_hi, qlo, qhi_unused;
   parse_i128(p_date->at("lo"), &dlo_lo, &dlo_hi);
   parse_i128(p_date->at("hi"), &dhi_lo, &dhi_hi);
@@ -1711,18 +1780,14 @@ static bool try_q6_fusion(const Value& agg_node, Metrics& m, Table* out) {
   Table res;
   res.n = 1;
   for (auto& a : aggs) {
-    Col c;
+    Col c = make_col({BG_DT_INT64, 0, 0});
     if (a->get_str("fn") == "sum") {
-      c.dtype = BG_DT_DECIMAL128;
-      c.precision = 38;
       // scale of the product = s1 + s2 from the scan schema
-      int s1 = t.cols[(size_t)t.idx(disc_name)].scale;
-      int s2 = t.cols[(size_t)t.idx(price_name)].scale;
-      c.scale = s1 + s2;
+      c = make_col({BG_DT_DECIMAL128, 38,
+                    t.col(disc_name).scale + t.col(price_name).scale});
       uint64_t host[2] = {sum_lo, (uint64_t)sum_hi};
       c.data = upload(host, 16);
     } else {
-      c.dtype = BG_DT_INT64;
       c.data = upload(&count, 8);
     }
     res.names.push_back(a->get_str("as"));
@@ -1732,14 +1797,264 @@ static bool try_q6_fusion(const Value& agg_node, Metrics& m, Table* out) {
   return true;
 }
 
+// ---- aggregate output schema: the one derivation that bg_stage_validate
+// and execution both read ----
+struct AggField {
+  std::string name;
+  DtSpec dt;
+};
+static const DtSpec DT_I64{BG_DT_INT64, 0, 0};
+
+static void check_agg_fn(const std::string& fn) {
+  if (fn != "sum" && fn != "min" && fn != "max" && fn != "count" &&
+      fn != "avg")
+    throw StageError(BG_ERR_INVALID, "aggregate fn " + fn);
+}
+
+// The partial-side columns of one aggregate, value first: what partial
+// mode emits and final mode reads.  A count is its own non-null count.
+static std::vector<std::string> agg_partial_names(const std::string& fn,
+                                                  const std::string& as) {
+  if (fn == "count") return {as};
+  return {fn == "avg" ? as + "$s" : as, as + "$n"};
+}
+
+// The output fields of one aggregate, in order.  `in` is the dtype of its
+// input: the evaluated expression (single/partial; unused by count) or the
+// partial value column (final).
+static std::vector<AggField> agg_output_fields(const std::string& fn,
+                                               const std::string& mode,
+                                               const std::string& as,
+                                               DtSpec in) {
+  check_agg_fn(fn);
+  if (fn == "count") return {{as, DT_I64}};
+  // a Decimal128 sum accumulates at full width
+  if (fn == "sum" && in.dt == BG_DT_DECIMAL128) in.precision = 38;
+  if (mode == "partial") {
+    auto names = agg_partial_names(fn, as);
+    return {{names[0], in}, {names[1], DT_I64}};
+  }
+  // DataFusion decimal AVG: out scale = in scale + 4, precision + 4
+  if (fn == "avg" && in.dt == BG_DT_FLOAT64) in = {BG_DT_FLOAT64, 0, 0};
+  else if (fn == "avg")
+    in = {BG_DT_DECIMAL128, std::min(in.precision + 4, 38), in.scale + 4};
+  return {{as, in}};
+}
+
 struct AggSpec {
   std::string fn, as;
-  int agg_slot = -1;   // index into the kernel's agg list (-1: count(*))
-  int nn_slot = -1;    // extra slot whose SUM carries the merged nn (final)
-  int32_t op = 0;      // kernel op for the value slot
-  int32_t in_dt = 0;   // input col dtype
-  int32_t in_prec = 0, in_scale = 0;
+  int agg_slot = -1;  // index into the kernel's agg list (-1: count(*))
+  int nn_slot = -1;   // extra slot whose SUM carries the merged nn (final)
+  int32_t op = 0;     // kernel op for the value slot
+  DtSpec in{0, 0, 0};  // input dtype, as agg_output_fields takes it
 };
+
+// The kernel's aggregate list: one slot per evaluated input column.
+struct AggSlots {
+  std::vector<AggSpec> specs;
+  std::vector<Col> in;
+  std::vector<int32_t> ops;
+  int add(const Col& c, int32_t op) {
+    in.push_back(c);
+    ops.push_back(op);
+    return (int)in.size() - 1;
+  }
+};
+
+static int32_t agg_op_for(const std::string& fn, int32_t dt) {
+  if (fn == "min" || fn == "max") {
+    if (dt == BG_DT_FLOAT64)
+      return fn == "min" ? BG_AGG_OP_MIN_F64 : BG_AGG_OP_MAX_F64;
+    if (dt != BG_DT_INT64)
+      throw StageError(BG_ERR_UNSUPPORTED, "min/max: int64/f64 only");
+    return fn == "min" ? BG_AGG_OP_MIN_I64 : BG_AGG_OP_MAX_I64;
+  }
+  switch (dt) {  // sum, avg and count(expr) all run a sum
+    case BG_DT_DECIMAL128: return BG_AGG_OP_SUM_DEC128;
+    case BG_DT_INT64: return BG_AGG_OP_SUM_I64;
+    case BG_DT_FLOAT64: return BG_AGG_OP_SUM_F64;
+    default:
+      throw StageError(BG_ERR_UNSUPPORTED, "sum over unsupported dtype");
+  }
+}
+
+// Specs and kernel input columns of a hash_aggregate node over its input.
+static AggSlots plan_agg_slots(const Value& node, const Table& in,
+                               bool is_final) {
+  auto& aggs = node.get_arr("aggs");
+  auto is_count_star = [](const Value& a) {
+    return a.get_str("fn") == "count" && !a.has("expr");
+  };
+  // single/partial: the inputs are expressions — arithmetic fuses into one
+  // projection pass (q1-class chains cost ~77 GB of intermediates otherwise)
+  std::vector<const Value*> pre_exprs;
+  for (auto& a : aggs)
+    if (!is_final && !is_count_star(*a)) pre_exprs.push_back(&a->at("expr"));
+  std::vector<Col> pre_cols;
+  if (!pre_exprs.empty()) eval_exprs_fused(in, pre_exprs, &pre_cols);
+
+  AggSlots slots;
+  size_t pre = 0;
+  for (auto& a : aggs) {
+    AggSpec s;
+    s.fn = a->get_str("fn");
+    s.as = a->get_str("as");
+    if (is_final) {
+      // final: the inputs are the partial columns; a merged count is the
+      // sum of the counts, as is the "$n" companion of every other fn
+      auto names = agg_partial_names(s.fn, s.as);
+      const Col& cv = in.col(names[0]);
+      if (s.fn == "count") {
+        s.op = BG_AGG_OP_SUM_I64;
+        s.agg_slot = slots.add(cv, s.op);
+      } else {
+        const Col& cn = in.col(names[1]);
+        s.in = cv.spec();
+        s.op = agg_op_for(s.fn, cv.dtype);
+        s.agg_slot = slots.add(cv, s.op);
+        s.nn_slot = slots.add(cn, BG_AGG_OP_SUM_I64);
+      }
+    } else if (!is_count_star(*a)) {  // COUNT(*): the kernel's group counts
+      const Col& v = pre_cols[pre++];
+      s.in = v.spec();
+      s.op = agg_op_for(s.fn, v.dtype);
+      s.agg_slot = slots.add(v, s.op);
+    }
+    slots.specs.push_back(s);
+  }
+  return slots;
+}
+
+// One finished bg_hashagg2 run: ng groups, interleaved per-slot records.
+struct HashAggRun {
+  DBufPtr first, acc, counts, nncnt;
+  int64_t ng = 0;
+  int32_t naggs = 0;
+  int64_t acc_stride() const { return (int64_t)naggs * 16; }
+  int64_t nn_stride() const { return (int64_t)naggs * 8; }
+  const uint8_t* acc_at(int slot) const {
+    return acc->u8() + (int64_t)slot * 16;
+  }
+  const int64_t* nn_at(int slot) const {
+    return (const int64_t*)(nncnt->u8() + (int64_t)slot * 8);
+  }
+};
+
+// run the kernel (auto-grow on table-full, like gpu.py)
+static HashAggRun run_hashagg_growing(const Value& node, const Table& in,
+                                      const std::vector<Col>& keys,
+                                      const AggSlots& slots,
+                                      const DBufPtr& mask) {
+  std::vector<bg_column> kcols, acols;
+  for (auto& c : keys) kcols.push_back(to_bg(c, in.n));
+  for (auto& c : slots.in) acols.push_back(to_bg(c, in.n));
+  if (acols.empty()) acols.push_back(bg_column{});
+  std::vector<int32_t> aops = slots.ops;
+  if (aops.empty()) aops.push_back(0);
+
+  HashAggRun r;
+  r.naggs = (int32_t)slots.in.size();
+  int64_t cap = node.get_int_or("estimated_groups", 1 << 16);
+  if (cap < 64) cap = 64;
+  for (int attempt = 0; attempt < 10; ++attempt) {
+    r.first = dalloc((uint64_t)cap * 4);
+    r.acc = dalloc_elems(r.naggs, (int64_t)cap * 16);
+    r.counts = dalloc((uint64_t)cap * 8);
+    r.nncnt = dalloc_elems(r.naggs, (int64_t)cap * 8);
+    int rc = bg_hashagg2(kcols.data(), (int32_t)kcols.size(), acols.data(),
+                         aops.data(), r.naggs, mask ? mask->u8() : nullptr,
+                         in.n, cap, (uint32_t*)r.first->p, r.acc->u8(),
+                         (int64_t*)r.counts->p, (int64_t*)r.nncnt->p, &r.ng);
+    if (rc == BG_OK) break;
+    std::string err = bg_last_error();
+    if (err.find("table full") == std::string::npos || cap >= in.n)
+      chk(rc, "bg_hashagg2");
+    cap = cap * 8 < in.n ? cap * 8 : (in.n > 64 ? in.n : 64);
+  }
+  return r;
+}
+
+// where a group's non-null count lives: the kernel's nn records, or in
+// final mode the merged "$n" sum (a SUM_I64 acc record's low limb)
+struct NnSrc {
+  const int64_t* p;
+  int64_t stride;
+};
+static NnSrc nn_source(const HashAggRun& r, const AggSpec& s, bool is_final) {
+  if (is_final) return {(const int64_t*)r.acc_at(s.nn_slot), r.acc_stride()};
+  return {r.nn_at(s.agg_slot), r.nn_stride()};
+}
+
+// the non-null count of a slot as an INT64 column (never NULL)
+static Col nn_column(const HashAggRun& r, int slot) {
+  Col cn = make_col(DT_I64);
+  cn.data = dalloc_elems(r.ng, 8);
+  chk(bg_copy_i64_strided(r.nn_at(slot), r.nn_stride(), r.ng, cn.data->p),
+      "bg_copy_i64_strided");
+  return cn;
+}
+
+// the decoded value of a spec's slot; with an nn source, NULL where every
+// input of the group was NULL
+static Col value_column(const HashAggRun& r, const AggSpec& s,
+                        const DtSpec& dt, const NnSrc* nn) {
+  Col cv = make_col(dt);
+  cv.data = dalloc_elems(r.ng, dt_size(dt.dt));
+  if (nn) cv.validity = alloc_bitmap(r.ng, 0xFF);
+  chk(bg_agg_materialize(r.acc_at(s.agg_slot), r.acc_stride(), s.op, r.ng,
+                         cv.data->p, nn ? nn->p : nullptr,
+                         nn ? nn->stride : 0,
+                         nn ? cv.validity->u8() : nullptr),
+      "bg_agg_materialize");
+  return cv;
+}
+
+static Col avg_column(const HashAggRun& r, const AggSpec& s, const DtSpec& dt,
+                      const NnSrc& nn) {
+  Col cv = make_col(dt);
+  cv.data = dalloc_elems(r.ng, dt_size(dt.dt));
+  cv.validity = alloc_bitmap(r.ng, 0xFF);
+  chk(bg_avg_finalize(r.acc_at(s.agg_slot), r.acc_stride(),
+                      dt.dt == BG_DT_FLOAT64 ? 1 : 0, nn.p, nn.stride, 4, r.ng,
+                      cv.data->p, cv.validity->u8()),
+      "bg_avg_finalize");
+  return cv;
+}
+
+// Append every aggregate's output columns; names and dtypes come from
+// agg_output_fields.
+static void materialize_aggs(const std::vector<AggSpec>& specs,
+                             const std::string& mode, const HashAggRun& r,
+                             Table& out) {
+  const bool is_final = mode == "final", is_partial = mode == "partial";
+  for (auto& s : specs) {
+    const auto fields = agg_output_fields(s.fn, mode, s.as, s.in);
+    const DtSpec& dt = fields[0].dt;
+    std::vector<Col> cols;
+    if (s.agg_slot < 0) {
+      // COUNT(*) = the group counts: dense i64[ng] already, never NULL
+      cols.push_back(make_col(dt));
+      cols[0].data = r.counts;
+    } else if (s.fn == "count") {
+      // final: the merged count is the SUM_I64 acc itself
+      cols.push_back(is_final ? value_column(r, s, dt, nullptr)
+                              : nn_column(r, s.agg_slot));
+    } else if (s.fn == "avg" && !is_partial) {
+      cols.push_back(avg_column(r, s, dt, nn_source(r, s, is_final)));
+    } else {
+      // sum/min/max, and the "$s" sum of a partial avg (never NULL: its
+      // "$n" companion says when it is empty)
+      const NnSrc nn = nn_source(r, s, is_final);
+      cols.push_back(
+          value_column(r, s, dt, s.fn == "avg" ? nullptr : &nn));
+      if (is_partial) cols.push_back(nn_column(r, s.agg_slot));
+    }
+    for (size_t i = 0; i < cols.size(); ++i) {
+      out.names.push_back(fields[i].name);
+      out.cols.push_back(std::move(cols[i]));
+    }
+  }
+}
 
 static Table exec_aggregate(const Value& node, Metrics& m) {
   {
@@ -1747,8 +2062,6 @@ static Table exec_aggregate(const Value& node, Metrics& m) {
     if (try_q6_fusion(node, m, &fused)) return fused;
   }
   const std::string mode = node.get_str_or("mode", "single");
-  const bool is_final = (mode == "final");
-  const bool is_partial = (mode == "partial");
 
   // input (+ fused filter mask when the child is a filter)
   DBufPtr mask;
@@ -1761,335 +2074,44 @@ static Table exec_aggregate(const Value& node, Metrics& m) {
     in = exec_plan(child, m);
   }
 
-  // group keys
-  std::vector<int> key_ids;
-  for (auto& k : node.get_arr("group_by"))
-    key_ids.push_back(in.idx(k->s));
-  bool const_key = key_ids.empty();
-  Col const_key_col;
-  if (const_key) {
-    const_key_col.dtype = BG_DT_INT64;
-    const_key_col.data = dalloc((uint64_t)(in.n > 0 ? in.n : 1) * 8);
-    chk(bg_memset(const_key_col.data->p, 0, const_key_col.data->bytes),
-        "bg_memset");
+  // group keys; none = one group under a constant key
+  auto& group_by = node.get_arr("group_by");
+  std::vector<Col> keys;
+  for (auto& k : group_by) keys.push_back(in.col(k->s));
+  if (keys.empty()) {
+    keys.push_back(make_col(DT_I64));
+    keys[0].data = dalloc_elems(in.n, 8);
+    chk(bg_memset(keys[0].data->p, 0, keys[0].data->bytes), "bg_memset");
   }
 
-  // aggregate inputs — arithmetic expressions fuse into one projection
-  // pass (q1-class chains cost ~77 GB of intermediates otherwise)
-  std::vector<const Value*> pre_exprs;
-  std::vector<size_t> pre_idx;
-  {
-    size_t ai = 0;
-    for (auto& a : node.get_arr("aggs")) {
-      const std::string fn = a->get_str("fn");
-      if (!is_final && a->has("expr") && !(fn == "count" && !a->has("expr"))) {
-        pre_exprs.push_back(&a->at("expr"));
-        pre_idx.push_back(ai);
-      }
-      ++ai;
-    }
-  }
-  std::vector<Col> pre_cols;
-  if (!pre_exprs.empty()) eval_exprs_fused(in, pre_exprs, &pre_cols);
-  auto pre_col_of = [&](size_t agg_index) -> Col* {
-    for (size_t i = 0; i < pre_idx.size(); ++i)
-      if (pre_idx[i] == agg_index) return &pre_cols[i];
-    return nullptr;
-  };
-  size_t agg_index = 0;
+  AggSlots slots = plan_agg_slots(node, in, mode == "final");
+  HashAggRun r = run_hashagg_growing(node, in, keys, slots, mask);
 
-  std::vector<AggSpec> specs;
-  std::vector<Col> agg_in;       // evaluated agg input columns
-  std::vector<int32_t> agg_ops;
-  auto add_slot = [&](const Col& c, int32_t op) {
-    agg_in.push_back(c);
-    agg_ops.push_back(op);
-    return (int)agg_in.size() - 1;
-  };
-  auto sum_op_for = [&](const Col& c) -> int32_t {
-    switch (c.dtype) {
-      case BG_DT_DECIMAL128: return BG_AGG_OP_SUM_DEC128;
-      case BG_DT_INT64: return BG_AGG_OP_SUM_I64;
-      case BG_DT_FLOAT64: return BG_AGG_OP_SUM_F64;
-      default:
-        throw StageError(BG_ERR_UNSUPPORTED, "sum over unsupported dtype");
-    }
-  };
-
-  for (auto& a : node.get_arr("aggs")) {
-    AggSpec s;
-    s.fn = a->get_str("fn");
-    s.as = a->get_str("as");
-    if (is_final) {
-      // inputs are the partial columns named "<as>" / "<as>$n" / "<as>$s"
-      if (s.fn == "count") {
-        const Col& c = in.cols[(size_t)in.idx(s.as)];
-        s.agg_slot = add_slot(c, BG_AGG_OP_SUM_I64);
-        s.op = BG_AGG_OP_SUM_I64;
-      } else if (s.fn == "avg") {
-        const Col& cs = in.cols[(size_t)in.idx(s.as + "$s")];
-        const Col& cn = in.cols[(size_t)in.idx(s.as + "$n")];
-        s.op = sum_op_for(cs);
-        s.in_dt = cs.dtype; s.in_prec = cs.precision; s.in_scale = cs.scale;
-        s.agg_slot = add_slot(cs, s.op);
-        s.nn_slot = add_slot(cn, BG_AGG_OP_SUM_I64);
-      } else {  // sum / min / max merge
-        const Col& cv = in.cols[(size_t)in.idx(s.as)];
-        const Col& cn = in.cols[(size_t)in.idx(s.as + "$n")];
-        s.in_dt = cv.dtype; s.in_prec = cv.precision; s.in_scale = cv.scale;
-        if (s.fn == "sum") s.op = sum_op_for(cv);
-        else if (s.fn == "min")
-          s.op = cv.dtype == BG_DT_FLOAT64 ? BG_AGG_OP_MIN_F64
-                                           : BG_AGG_OP_MIN_I64;
-        else
-          s.op = cv.dtype == BG_DT_FLOAT64 ? BG_AGG_OP_MAX_F64
-                                           : BG_AGG_OP_MAX_I64;
-        if (s.op == BG_AGG_OP_MIN_I64 || s.op == BG_AGG_OP_MAX_I64) {
-          if (cv.dtype != BG_DT_INT64)
-            throw StageError(BG_ERR_UNSUPPORTED, "min/max: int64/f64 only");
-        }
-        s.agg_slot = add_slot(cv, s.op);
-        s.nn_slot = add_slot(cn, BG_AGG_OP_SUM_I64);
-      }
-    } else {
-      if (s.fn == "count" && !a->has("expr")) {
-        s.agg_slot = -1;  // COUNT(*): the kernel's group counts
-      } else {
-        ExprVal v;
-        Col* pc = pre_col_of(agg_index);
-        if (pc) v.col = *pc;
-        else {
-          v = eval_expr(in, a->at("expr"));
-          if (v.is_lit)
-            throw StageError(BG_ERR_INVALID, "aggregate of a literal");
-        }
-        s.in_dt = v.col.dtype; s.in_prec = v.col.precision;
-        s.in_scale = v.col.scale;
-        if (s.fn == "sum" || s.fn == "avg" || s.fn == "count")
-          s.op = sum_op_for(v.col);
-        else if (s.fn == "min")
-          s.op = v.col.dtype == BG_DT_FLOAT64 ? BG_AGG_OP_MIN_F64
-                                              : BG_AGG_OP_MIN_I64;
-        else if (s.fn == "max")
-          s.op = v.col.dtype == BG_DT_FLOAT64 ? BG_AGG_OP_MAX_F64
-                                              : BG_AGG_OP_MAX_I64;
-        else
-          throw StageError(BG_ERR_UNSUPPORTED, "aggregate fn " + s.fn);
-        if ((s.op == BG_AGG_OP_MIN_I64 || s.op == BG_AGG_OP_MAX_I64) &&
-            v.col.dtype != BG_DT_INT64)
-          throw StageError(BG_ERR_UNSUPPORTED, "min/max: int64/f64 only");
-        s.agg_slot = add_slot(v.col, s.op);
-      }
-    }
-    specs.push_back(s);
-    ++agg_index;
-  }
-
-  // run the kernel (auto-grow on table-full, like gpu.py)
-  std::vector<bg_column> kcols;
-  if (const_key) kcols.push_back(to_bg(const_key_col, in.n));
-  else
-    for (int ki : key_ids) kcols.push_back(to_bg(in.cols[(size_t)ki], in.n));
-  std::vector<bg_column> acols;
-  for (auto& c : agg_in) acols.push_back(to_bg(c, in.n));
-  if (acols.empty()) acols.push_back(bg_column{});
-  std::vector<int32_t> aops = agg_ops;
-  if (aops.empty()) aops.push_back(0);
-  int32_t naggs = (int32_t)agg_in.size();
-
-  int64_t cap = node.get_int_or("estimated_groups", 1 << 16);
-  if (cap < 64) cap = 64;
-  DBufPtr first, acc, counts, nncnt;
-  int64_t ng = 0;
-  for (int attempt = 0; attempt < 10; ++attempt) {
-    first = dalloc((uint64_t)cap * 4);
-    acc = dalloc((uint64_t)cap * (uint64_t)(naggs > 0 ? naggs : 1) * 16);
-    counts = dalloc((uint64_t)cap * 8);
-    nncnt = dalloc((uint64_t)cap * (uint64_t)(naggs > 0 ? naggs : 1) * 8);
-    int rc = bg_hashagg2(kcols.data(), (int32_t)kcols.size(), acols.data(),
-                         aops.data(), naggs, mask ? mask->u8() : nullptr,
-                         in.n, cap, (uint32_t*)first->p, acc->u8(),
-                         (int64_t*)counts->p, (int64_t*)nncnt->p, &ng);
-    if (rc == BG_OK) break;
-    std::string err = bg_last_error();
-    if (err.find("table full") == std::string::npos || cap >= in.n)
-      chk(rc, "bg_hashagg2");
-    cap = cap * 8 < in.n ? cap * 8 : (in.n > 64 ? in.n : 64);
-  }
-
-  // materialize output columns
   Table out;
-  out.n = ng;
+  out.n = r.ng;
   // group keys (gathered by first_row; NULL keys keep their validity)
-  if (!const_key) {
-    for (size_t i = 0; i < key_ids.size(); ++i) {
-      out.names.push_back(node.get_arr("group_by")[i]->s);
-      out.cols.push_back(gather_col(in.cols[(size_t)key_ids[i]], in.n,
-                                    (const uint32_t*)first->p, ng));
-    }
+  for (size_t i = 0; i < group_by.size(); ++i) {
+    out.names.push_back(group_by[i]->s);
+    out.cols.push_back(
+        gather_col(keys[i], in.n, (const uint32_t*)r.first->p, r.ng));
   }
-  int64_t acc_stride = (int64_t)naggs * 16;
-  int64_t nn_stride = (int64_t)naggs * 8;
-  auto acc_at = [&](int slot) { return acc->u8() + (int64_t)slot * 16; };
-  auto nn_at = [&](int slot) {
-    return (const int64_t*)(nncnt->u8() + (int64_t)slot * 8);
-  };
-  auto alloc_valid = [&]() {
-    DBufPtr v = dalloc((uint64_t)((ng + 63) / 64) * 8 + 8);
-    chk(bg_memset(v->p, 0xFF, v->bytes), "bg_memset");
-    return v;
-  };
-
-  for (auto& s : specs) {
-    Col c;
-    if (s.fn == "count" && s.agg_slot == -1) {
-      // COUNT(*) = the group counts (never NULL)
-      c.dtype = BG_DT_INT64;
-      c.data = counts;  // dense i64[ng] already
-      out.names.push_back(s.as);
-      out.cols.push_back(std::move(c));
-      continue;
-    }
-    if (is_partial) {
-      // value column + "$n" companion
-      if (s.fn == "avg") {
-        Col cs;
-        cs.dtype = s.in_dt; cs.precision = s.in_prec; cs.scale = s.in_scale;
-        int64_t esz = cs.dtype == BG_DT_DECIMAL128 ? 16 : 8;
-        cs.data = dalloc((uint64_t)(ng > 0 ? ng : 1) * (uint64_t)esz);
-        chk(bg_agg_materialize(acc_at(s.agg_slot), acc_stride, s.op, ng,
-                               cs.data->p, nullptr, 0, nullptr),
-            "bg_agg_materialize");
-        out.names.push_back(s.as + "$s");
-        out.cols.push_back(std::move(cs));
-        Col cn;
-        cn.dtype = BG_DT_INT64;
-        cn.data = dalloc((uint64_t)(ng > 0 ? ng : 1) * 8);
-        chk(bg_copy_i64_strided(nn_at(s.agg_slot), nn_stride, ng, cn.data->p),
-            "bg_copy_i64_strided");
-        out.names.push_back(s.as + "$n");
-        out.cols.push_back(std::move(cn));
-        continue;
-      }
-      if (s.fn == "count") {
-        Col cn;
-        cn.dtype = BG_DT_INT64;
-        cn.data = dalloc((uint64_t)(ng > 0 ? ng : 1) * 8);
-        chk(bg_copy_i64_strided(nn_at(s.agg_slot), nn_stride, ng, cn.data->p),
-            "bg_copy_i64_strided");
-        out.names.push_back(s.as);
-        out.cols.push_back(std::move(cn));
-        continue;
-      }
-      // sum/min/max partial: decoded value (+ NULL when all inputs NULL)
-      Col cv;
-      cv.dtype = s.in_dt; cv.precision = s.in_prec; cv.scale = s.in_scale;
-      if (s.fn == "sum" && s.in_dt == BG_DT_DECIMAL128) {
-        cv.precision = 38;
-      }
-      int64_t esz = cv.dtype == BG_DT_DECIMAL128 ? 16 : 8;
-      cv.data = dalloc((uint64_t)(ng > 0 ? ng : 1) * (uint64_t)esz);
-      cv.validity = alloc_valid();
-      chk(bg_agg_materialize(acc_at(s.agg_slot), acc_stride, s.op, ng,
-                             cv.data->p, nn_at(s.agg_slot), nn_stride,
-                             cv.validity->u8()),
-          "bg_agg_materialize");
-      out.names.push_back(s.as);
-      out.cols.push_back(std::move(cv));
-      Col cn;
-      cn.dtype = BG_DT_INT64;
-      cn.data = dalloc((uint64_t)(ng > 0 ? ng : 1) * 8);
-      chk(bg_copy_i64_strided(nn_at(s.agg_slot), nn_stride, ng, cn.data->p),
-          "bg_copy_i64_strided");
-      out.names.push_back(s.as + "$n");
-      out.cols.push_back(std::move(cn));
-      continue;
-    }
-    // single/final: finalized value
-    if (s.fn == "count") {
-      Col cn;
-      cn.dtype = BG_DT_INT64;
-      cn.data = dalloc((uint64_t)(ng > 0 ? ng : 1) * 8);
-      if (is_final) {
-        // merged count lives in the SUM_I64 acc (i128 low limb)
-        chk(bg_agg_materialize(acc_at(s.agg_slot), acc_stride,
-                               BG_AGG_OP_SUM_I64, ng, cn.data->p, nullptr, 0,
-                               nullptr),
-            "bg_agg_materialize");
-      } else {
-        chk(bg_copy_i64_strided(nn_at(s.agg_slot), nn_stride, ng, cn.data->p),
-            "bg_copy_i64_strided");
-      }
-      out.names.push_back(s.as);
-      out.cols.push_back(std::move(cn));
-      continue;
-    }
-    if (s.fn == "avg") {
-      // DataFusion decimal AVG: out scale = in scale + 4, precision +4
-      bool is_f64 = (s.in_dt == BG_DT_FLOAT64);
-      Col cv;
-      cv.dtype = is_f64 ? BG_DT_FLOAT64 : BG_DT_DECIMAL128;
-      cv.precision = is_f64 ? 0 : (s.in_prec + 4 > 38 ? 38 : s.in_prec + 4);
-      cv.scale = is_f64 ? 0 : s.in_scale + 4;
-      cv.data = dalloc((uint64_t)(ng > 0 ? ng : 1) * (is_f64 ? 8 : 16));
-      cv.validity = alloc_valid();
-      const void* cnt_ptr;
-      int64_t cnt_stride;
-      if (is_final) {  // merged nn is a SUM_I64 acc: low limb, stride 16*naggs
-        cnt_ptr = acc_at(s.nn_slot);
-        cnt_stride = acc_stride;
-      } else {
-        cnt_ptr = nn_at(s.agg_slot);
-        cnt_stride = nn_stride;
-      }
-      chk(bg_avg_finalize(acc_at(s.agg_slot), acc_stride, is_f64 ? 1 : 0,
-                          cnt_ptr, cnt_stride, 4, ng, cv.data->p,
-                          cv.validity->u8()),
-          "bg_avg_finalize");
-      out.names.push_back(s.as);
-      out.cols.push_back(std::move(cv));
-      continue;
-    }
-    // sum/min/max finalized
-    Col cv;
-    cv.dtype = s.in_dt ? s.in_dt : BG_DT_DECIMAL128;
-    cv.precision = s.in_prec; cv.scale = s.in_scale;
-    if (s.fn == "sum" && cv.dtype == BG_DT_DECIMAL128) cv.precision = 38;
-    int64_t esz = cv.dtype == BG_DT_DECIMAL128 ? 16 : 8;
-    cv.data = dalloc((uint64_t)(ng > 0 ? ng : 1) * (uint64_t)esz);
-    cv.validity = alloc_valid();
-    const int64_t* nnp;
-    int64_t nns;
-    if (is_final) {
-      nnp = (const int64_t*)acc_at(s.nn_slot);  // SUM_I64 acc low limb
-      nns = acc_stride;
-    } else {
-      nnp = nn_at(s.agg_slot);
-      nns = nn_stride;
-    }
-    chk(bg_agg_materialize(acc_at(s.agg_slot), acc_stride, s.op, ng,
-                           cv.data->p, nnp, nns, cv.validity->u8()),
-        "bg_agg_materialize");
-    out.names.push_back(s.as);
-    out.cols.push_back(std::move(cv));
-  }
-  m.output_rows = ng;
+  materialize_aggs(slots.specs, mode, r, out);
+  m.output_rows = r.ng;
   return out;
 }
-
 static Table exec_sort(const Value& node, Metrics& m) {
   Table in = exec_plan(node.at("input"), m);
   auto& keys = node.get_arr("keys");
   std::vector<bg_column> kcols;
   std::vector<int32_t> desc, nf;
   for (auto& k : keys) {
-    kcols.push_back(to_bg(in.cols[(size_t)in.idx(k->get_str("col"))], in.n));
+    kcols.push_back(to_bg(in.col(k->get_str("col")), in.n));
     bool d = k->get_bool_or("desc", false);
     desc.push_back(d ? 1 : 0);
     // SQL default: ASC => NULLS LAST, DESC => NULLS FIRST
     nf.push_back(k->get_bool_or("nulls_first", d) ? 1 : 0);
   }
-  DBufPtr perm = dalloc((uint64_t)(in.n > 0 ? in.n : 1) * 4);
+  DBufPtr perm = dalloc_elems(in.n, 4);
   chk(bg_sort_rows2(kcols.data(), desc.data(), nf.data(),
                     (int32_t)kcols.size(), in.n, (uint32_t*)perm->p),
       "bg_sort_rows2");
@@ -2101,11 +2123,9 @@ static Table exec_sort(const Value& node, Metrics& m) {
 static Table exec_plan(const Value& node, Metrics& m) {
   const std::string op = node.get_str("op");
   if (op == "scan") {
-    auto t0 = std::chrono::steady_clock::now();
+    auto t0 = Clock::now();
     Table t = scan(node);
-    m.scan_time_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(
-                          std::chrono::steady_clock::now() - t0)
-                          .count();
+    m.scan_time_ns += ns_since(t0);
     return t;
   }
   if (op == "filter") {
@@ -2161,97 +2181,147 @@ struct WriteStats {
   int64_t num_batches = 0, num_rows = 0, num_bytes = 0;
 };
 
-// Compress every batch buffer of every partition on device in ONE flat
-// launch, pack the [u32 size][block] bodies at final offsets in ONE
-// launch, then stream the file: host metadata interleaved with slices of
-// a single packed D2H download.  (The device half of
-// encode_buffered_partitions + write_task_consolidated.)
-static void write_consolidated(
-    const std::string& data_path, const std::string& index_path,
-    const std::vector<uint8_t>& schema_msg,
-    std::vector<std::vector<EncBatch>>& parts,  // per partition
-    std::vector<WriteStats>* stats, std::vector<int64_t>* offsets_out,
-    bool leading_schema_stream = true, bool always_stream = false) {
-  size_t k = parts.size();
-  // flat LZ4 block jobs
-  struct BufRef { size_t p, b, s; int64_t len, job0; int nblocks; };
+// LZ4 block i of a buffer of len bytes: every block full but the last
+static int32_t block_len(int64_t len, int64_t i) {
+  return (int32_t)std::min<int64_t>(len - i * BG_LZ4_BLOCK, BG_LZ4_BLOCK);
+}
+
+// One non-empty buffer (partition p, batch b, slot s) and its block jobs.
+struct BufRef { size_t p, b, s; int64_t len, job0; int nblocks; };
+struct CompressedBlocks {
   std::vector<BufRef> refs;
   std::vector<bg_lz4_block_job> jobs;
-  int64_t slot_cursor = 0;
-  DBufPtr slots;
-  {
-    std::vector<std::pair<const uint8_t*, int32_t>> blocks;
-    for (size_t p = 0; p < k; ++p)
-      for (size_t b = 0; b < parts[p].size(); ++b)
-        for (size_t s = 0; s < parts[p][b].bufs.size(); ++s) {
-          auto& eb = parts[p][b].bufs[s];
-          if (eb.len <= 0) continue;
-          int nb = (int)((eb.len + BG_LZ4_BLOCK - 1) / BG_LZ4_BLOCK);
-          refs.push_back({p, b, s, eb.len, (int64_t)blocks.size(), nb});
-          for (int i = 0; i < nb; ++i) {
-            int32_t blen = (int32_t)(eb.len - (int64_t)i * BG_LZ4_BLOCK <
-                                             BG_LZ4_BLOCK
-                                         ? eb.len - (int64_t)i * BG_LZ4_BLOCK
-                                         : BG_LZ4_BLOCK);
-            blocks.push_back(
-                {(const uint8_t*)eb.dptr + (int64_t)i * BG_LZ4_BLOCK, blen});
-          }
-        }
-    slots = dalloc((uint64_t)(blocks.size() ? blocks.size() : 1) *
-                   BG_LZ4_SLOT_STRIDE);
-    for (size_t i = 0; i < blocks.size(); ++i)
-      jobs.push_back({blocks[i].first,
-                      slots->u8() + (int64_t)i * BG_LZ4_SLOT_STRIDE,
-                      blocks[i].second, 0});
-  }
-  std::vector<int64_t> sizes(jobs.size());
-  if (!jobs.empty())
-    chk(bg_lz4_compress_flat(jobs.data(), (int64_t)jobs.size(), sizes.data()),
-        "bg_lz4_compress_flat");
+  DBufPtr slots;               // one BG_LZ4_SLOT_STRIDE slot per job
+  std::vector<int64_t> sizes;  // per job; negative = stored raw
+};
+// (p,b,s) -> (offset in the packed download, frame body length)
+using PackedAt =
+    std::map<std::tuple<size_t, size_t, size_t>, std::pair<int64_t, int64_t>>;
 
-  // frame body length per buffer and pack jobs at final packed offsets
-  std::map<std::tuple<size_t, size_t, size_t>, std::pair<int64_t, int64_t>>
-      packed_at;  // (p,b,s) -> (packed_off, body_len)
+// every batch buffer of every partition through ONE flat LZ4 launch
+static CompressedBlocks compress_blocks(
+    const std::vector<std::vector<EncBatch>>& parts) {
+  CompressedBlocks c;
+  for (size_t p = 0; p < parts.size(); ++p)
+    for (size_t b = 0; b < parts[p].size(); ++b)
+      for (size_t s = 0; s < parts[p][b].bufs.size(); ++s) {
+        auto& eb = parts[p][b].bufs[s];
+        if (eb.len <= 0) continue;
+        int nb = (int)((eb.len + BG_LZ4_BLOCK - 1) / BG_LZ4_BLOCK);
+        c.refs.push_back({p, b, s, eb.len, (int64_t)c.jobs.size(), nb});
+        for (int i = 0; i < nb; ++i)
+          c.jobs.push_back(
+              {(const uint8_t*)eb.dptr + (int64_t)i * BG_LZ4_BLOCK, nullptr,
+               block_len(eb.len, i), 0});
+      }
+  c.slots = dalloc_elems((int64_t)c.jobs.size(), BG_LZ4_SLOT_STRIDE);
+  for (size_t i = 0; i < c.jobs.size(); ++i)
+    c.jobs[i].d_dst_slot = c.slots->u8() + (int64_t)i * BG_LZ4_SLOT_STRIDE;
+  c.sizes.resize(c.jobs.size());
+  if (!c.jobs.empty())
+    chk(bg_lz4_compress_flat(c.jobs.data(), (int64_t)c.jobs.size(),
+                             c.sizes.data()),
+        "bg_lz4_compress_flat");
+  return c;
+}
+
+// pack the [u32 size][block] frame bodies back to back in ONE launch and
+// download them once; packed_at records where each buffer's body lies
+static std::vector<uint8_t> pack_bodies(const CompressedBlocks& c,
+                                        PackedAt* packed_at) {
   std::vector<bg_pack_job> pack_jobs;
-  int64_t packed_cursor = 0;
-  for (auto& r : refs) {
+  std::vector<int64_t> dst_offs;  // each job's offset in the packed buffer
+  int64_t cursor = 0;
+  for (auto& r : c.refs) {
     int64_t body = 0;
+    const int64_t start = cursor;
     for (int i = 0; i < r.nblocks; ++i) {
-      int64_t sz = sizes[(size_t)(r.job0 + i)];
+      const int64_t sz = c.sizes[(size_t)(r.job0 + i)];
+      const int32_t blen = block_len(r.len, i);
+      const int64_t payload = sz < 0 ? blen : sz;
+      const uint32_t word =
+          sz < 0 ? ((uint32_t)blen | 0x80000000u) : (uint32_t)sz;
+      pack_jobs.push_back(
+          {c.jobs[(size_t)(r.job0 + i)].d_dst_slot, nullptr, payload, word, 0});
+      dst_offs.push_back(cursor);
+      cursor += 4 + payload;
       body += 4 + (sz < 0 ? -sz : sz);
     }
-    packed_at[{r.p, r.b, r.s}] = {packed_cursor, body};
-    int64_t off = packed_cursor;
-    for (int i = 0; i < r.nblocks; ++i) {
-      int64_t sz = sizes[(size_t)(r.job0 + i)];
-      int32_t blen = (int32_t)(r.len - (int64_t)i * BG_LZ4_BLOCK < BG_LZ4_BLOCK
-                                   ? r.len - (int64_t)i * BG_LZ4_BLOCK
-                                   : BG_LZ4_BLOCK);
-      int64_t payload = sz < 0 ? blen : sz;
-      uint32_t word = sz < 0 ? ((uint32_t)blen | 0x80000000u) : (uint32_t)sz;
-      pack_jobs.push_back({jobs[(size_t)(r.job0 + i)].d_dst_slot,
-                           nullptr /* set below */, payload, word, 0});
-      // we cannot set d_dst before the packed buffer exists; record offset
-      pack_jobs.back()._pad = 0;
-      pack_jobs.back().d_dst = (uint8_t*)(uintptr_t)off;  // offset placeholder
-      off += 4 + payload;
-    }
-    packed_cursor += off - packed_cursor;
+    (*packed_at)[{r.p, r.b, r.s}] = {start, body};
   }
-  DBufPtr packed = dalloc((uint64_t)(packed_cursor ? packed_cursor : 1));
-  for (auto& pj : pack_jobs)
-    pj.d_dst = packed->u8() + (int64_t)(uintptr_t)pj.d_dst;
+  DBufPtr packed = dalloc_elems(cursor);
+  for (size_t i = 0; i < pack_jobs.size(); ++i)
+    pack_jobs[i].d_dst = packed->u8() + dst_offs[i];
   if (!pack_jobs.empty())
     chk(bg_pack_blocks(pack_jobs.data(), (int64_t)pack_jobs.size()),
         "bg_pack_blocks");
   chk(bg_synchronize(), "bg_synchronize");
 
-  std::vector<uint8_t> packed_host((size_t)(packed_cursor ? packed_cursor : 1));
-  if (packed_cursor)
-    chk(bg_memcpy_d2h(packed_host.data(), packed->p, (uint64_t)packed_cursor),
+  std::vector<uint8_t> host((size_t)(cursor ? cursor : 1));
+  if (cursor)
+    chk(bg_memcpy_d2h(host.data(), packed->p, (uint64_t)cursor),
         "bg_memcpy_d2h");
+  return host;
+}
 
-  // stream the file
+// one record batch of partition p: metadata, then per buffer
+// [i64 usize][LZ4 frame header][body][end mark], each 8-aligned
+static void stream_batch(FILE* f, const EncBatch& eb, size_t p, size_t b,
+                         const PackedAt& packed_at,
+                         const std::vector<uint8_t>& packed_host,
+                         WriteStats* stats) {
+  std::vector<bgipc::BufSpec> bufspecs;
+  int64_t body_len = 0;
+  std::vector<std::pair<int64_t, int64_t>> emit;  // packed_at; -1 = absent
+  for (size_t s = 0; s < eb.bufs.size(); ++s) {
+    if (eb.bufs[s].len <= 0) {
+      bufspecs.push_back({body_len, 0});
+      emit.push_back({-1, 0});
+      continue;
+    }
+    auto pa = packed_at.at({p, b, s});
+    int64_t part_len = 8 + 7 + pa.second + 4;  // usize + hdr + body + end
+    bufspecs.push_back({body_len, part_len});
+    emit.push_back(pa);
+    body_len += part_len;
+    body_len += (-body_len) & 7;
+  }
+  std::string meta =
+      bgipc::record_batch_message(eb.rows, eb.nodes, bufspecs, body_len, true);
+  fwrite(meta.data(), 1, meta.size(), f);
+  int64_t written = 0;
+  for (size_t s = 0; s < eb.bufs.size(); ++s) {
+    if (emit[s].first < 0) continue;
+    int64_t usize = eb.bufs[s].len;
+    fwrite(&usize, 8, 1, f);
+    fwrite(LZ4F_HEADER, 1, 7, f);
+    fwrite(packed_host.data() + emit[s].first, 1, (size_t)emit[s].second, f);
+    const uint32_t endmark = 0;
+    fwrite(&endmark, 4, 1, f);
+    written += 8 + 7 + emit[s].second + 4;
+    int64_t pad = (-written) & 7;
+    if (pad) {
+      const uint64_t z = 0;
+      fwrite(&z, 1, (size_t)pad, f);
+      written += pad;
+    }
+    if (stats) stats->num_bytes += usize;
+  }
+  if (stats) {
+    stats->num_batches += 1;
+    stats->num_rows += eb.rows;
+  }
+}
+
+// host metadata interleaved with slices of the single packed download;
+// returns the K+1 partition offsets of the index file
+static std::vector<int64_t> stream_file(
+    const std::string& data_path, const std::vector<uint8_t>& schema_msg,
+    const std::vector<std::vector<EncBatch>>& parts,
+    const PackedAt& packed_at, const std::vector<uint8_t>& packed_host,
+    std::vector<WriteStats>* stats, bool leading_schema_stream,
+    bool always_stream) {
+  const size_t k = parts.size();
   FILE* f = fopen(data_path.c_str(), "wb");
   if (!f) throw StageError(BG_ERR_INVALID, "cannot create " + data_path);
   std::vector<char> iobuf(4 << 20);
@@ -2269,67 +2339,40 @@ static void write_consolidated(
     for (auto& b : parts[p]) any |= b.rows > 0;
     if (!any) continue;
     fwrite(schema_msg.data(), 1, schema_msg.size(), f);
-    for (size_t b = 0; b < parts[p].size(); ++b) {
-      auto& eb = parts[p][b];
-      if (eb.rows == 0) continue;
-      // body layout: per buffer [i64 usize][frame], 8-aligned
-      std::vector<bgipc::BufSpec> bufspecs;
-      int64_t body_len = 0;
-      std::vector<std::pair<int64_t, int64_t>> emit;  // (packed_off,body) per buffer; -1 absent
-      for (size_t s = 0; s < eb.bufs.size(); ++s) {
-        if (eb.bufs[s].len <= 0) {
-          bufspecs.push_back({body_len, 0});
-          emit.push_back({-1, 0});
-          continue;
-        }
-        auto pa = packed_at.at({p, b, s});
-        int64_t part_len = 8 + 7 + pa.second + 4;  // usize + hdr + body + end
-        bufspecs.push_back({body_len, part_len});
-        emit.push_back(pa);
-        body_len += part_len;
-        body_len += (-body_len) & 7;
-      }
-      std::string meta = bgipc::record_batch_message(eb.rows, eb.nodes,
-                                                     bufspecs, body_len, true);
-      fwrite(meta.data(), 1, meta.size(), f);
-      int64_t written = 0;
-      for (size_t s = 0; s < eb.bufs.size(); ++s) {
-        if (emit[s].first < 0) continue;
-        int64_t usize = eb.bufs[s].len;
-        fwrite(&usize, 8, 1, f);
-        fwrite(LZ4F_HEADER, 1, 7, f);
-        fwrite(packed_host.data() + emit[s].first, 1, (size_t)emit[s].second,
-               f);
-        const uint32_t endmark = 0;
-        fwrite(&endmark, 4, 1, f);
-        written += 8 + 7 + emit[s].second + 4;
-        int64_t pad = (-written) & 7;
-        if (pad) {
-          const uint64_t z = 0;
-          fwrite(&z, 1, (size_t)pad, f);
-          written += pad;
-        }
-        if (stats) (*stats)[p].num_bytes += usize;
-      }
-      if (stats) {
-        (*stats)[p].num_batches += 1;
-        (*stats)[p].num_rows += eb.rows;
-      }
-    }
+    for (size_t b = 0; b < parts[p].size(); ++b)
+      if (parts[p][b].rows != 0)
+        stream_batch(f, parts[p][b], p, b, packed_at, packed_host,
+                     stats ? &(*stats)[p] : nullptr);
     fwrite(bgipc::EOS, 1, 8, f);
   }
   offsets[k] = (int64_t)ftello(f);
   fclose(f);
+  return offsets;
+}
 
+// Compress every batch buffer of every partition on device in ONE flat
+// launch, pack the [u32 size][block] bodies at final offsets in ONE
+// launch, then stream the file.  (The device half of
+// encode_buffered_partitions + write_task_consolidated.)
+static void write_consolidated(
+    const std::string& data_path, const std::string& index_path,
+    const std::vector<uint8_t>& schema_msg,
+    const std::vector<std::vector<EncBatch>>& parts,  // per partition
+    std::vector<WriteStats>* stats, bool leading_schema_stream = true,
+    bool always_stream = false) {
+  CompressedBlocks c = compress_blocks(parts);
+  PackedAt packed_at;
+  std::vector<uint8_t> packed_host = pack_bodies(c, &packed_at);
+  std::vector<int64_t> offsets =
+      stream_file(data_path, schema_msg, parts, packed_at, packed_host, stats,
+                  leading_schema_stream, always_stream);
   if (!index_path.empty()) {
     FILE* fi = fopen(index_path.c_str(), "wb");
     if (!fi) throw StageError(BG_ERR_INVALID, "cannot create " + index_path);
-    fwrite(offsets.data(), 8, k + 1, fi);
+    fwrite(offsets.data(), 8, offsets.size(), fi);
     fclose(fi);
   }
-  if (offsets_out) *offsets_out = offsets;
 }
-
 // Build the per-partition batch list for the hash-repartitioned table.
 static void build_repartition_batches(
     const Table& t, uint32_t kparts, int64_t batch_size,
@@ -2350,7 +2393,7 @@ static void build_repartition_batches(
       int64_t lo = offsets_host[p], hi = offsets_host[p + 1];
       int64_t mrows = hi - lo;
       if (mrows == 0) continue;
-      DBufPtr vb = dalloc((uint64_t)((mrows + 63) / 64) * 8 + 8);
+      DBufPtr vb = alloc_bitmap(mrows);
       chk(bg_gather_bits(t.cols[c].vptr(), (const uint32_t*)idx->u8() + lo,
                          mrows, vb->u8()),
           "bg_gather_bits");
@@ -2432,6 +2475,32 @@ static void build_repartition_batches(
   for (auto& kv : part_valid) keepalive->push_back(kv.second);
 }
 
+// {work_dir}/{job}/{stage}/{leaf}, created
+static std::string task_dir(const Value& doc, int64_t leaf) {
+  std::string dir = doc.get_str("work_dir") + "/" + doc.get_str("job_id") +
+                    "/" + std::to_string(doc.get_int("stage_id")) + "/" +
+                    std::to_string(leaf);
+  mkdirs(dir);
+  return dir;
+}
+
+// one {...} entry of the result's "partitions" list
+static void emit_partition_json(bgjson::Writer& res, int64_t id,
+                                const std::string& path,
+                                const WriteStats& stats) {
+  res.raw("{\"partition_id\":");
+  res.num(id);
+  res.raw(",\"path\":");
+  res.str(path);
+  res.raw(",\"num_batches\":");
+  res.num(stats.num_batches);
+  res.raw(",\"num_rows\":");
+  res.num(stats.num_rows);
+  res.raw(",\"num_bytes\":");
+  res.num(stats.num_bytes);
+  res.raw("}");
+}
+
 static void exec_sort_shuffle_write(const Value& root, const Value& plan_doc,
                                     Metrics& m, bgjson::Writer& res) {
   Table t = exec_plan(root.at("input"), m);
@@ -2442,7 +2511,7 @@ static void exec_sort_shuffle_write(const Value& root, const Value& plan_doc,
     throw StageError(BG_ERR_INVALID, "batch_size must be a multiple of 8");
   auto schema_msg = hex_decode(plan_doc.get_str("schema_msg_hex"));
 
-  auto t0 = std::chrono::steady_clock::now();
+  auto t0 = Clock::now();
   // key EXPRESSIONS evaluated before hashing (writer.rs:1265, 1259-1279)
   std::vector<Col> key_cols_own;
   for (auto& ke : root.get_arr("keys")) {
@@ -2462,13 +2531,12 @@ static void exec_sort_shuffle_write(const Value& root, const Value& plan_doc,
     payload.push_back(to_bg(t.cols[c], t.n));
   }
 
-  DBufPtr idx = dalloc((uint64_t)(t.n > 0 ? t.n : 1) * 4);
+  DBufPtr idx = dalloc_elems(t.n, 4);
   DBufPtr offs = dalloc((uint64_t)(kparts + 1) * 8);
   std::vector<DBufPtr> fixed_out;
   std::vector<void*> outp;
   for (int c : fixed_ids) {
-    int64_t esz = dt_size(t.cols[(size_t)c].dtype);
-    fixed_out.push_back(dalloc((uint64_t)(t.n > 0 ? t.n : 1) * (uint64_t)esz));
+    fixed_out.push_back(dalloc_elems(t.n, dt_size(t.cols[(size_t)c].dtype)));
     outp.push_back(fixed_out.back()->p);
   }
   chk(bg_hash_repartition(kcols.data(), (int32_t)kcols.size(), payload.data(),
@@ -2478,9 +2546,9 @@ static void exec_sort_shuffle_write(const Value& root, const Value& plan_doc,
   // variable-length payload through the same permutation
   for (size_t c = 0; c < t.cols.size(); ++c) {
     if (t.cols[c].dtype != BG_DT_UTF8) continue;
-    int64_t cap = t.cols[c].data_bytes > 0 ? t.cols[c].data_bytes : 1;
     DBufPtr oo = dalloc((uint64_t)(t.n + 1) * 4);
-    DBufPtr od = dalloc((uint64_t)cap);
+    DBufPtr od = dalloc_elems(t.cols[c].data_bytes);
+    const int64_t cap = (int64_t)od->bytes;
     int64_t tot = 0;
     chk(bg_gather_varlen(t.cols[c].dptr(), t.cols[c].optr(),
                          (const uint32_t*)idx->p, t.n, (int32_t*)oo->p,
@@ -2492,11 +2560,9 @@ static void exec_sort_shuffle_write(const Value& root, const Value& plan_doc,
   chk(bg_memcpy_d2h(offsets_host.data(), offs->p, (kparts + 1) * 8),
       "bg_memcpy_d2h");
   chk(bg_synchronize(), "bg_synchronize");
-  m.repart_time_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(
-                         std::chrono::steady_clock::now() - t0)
-                         .count();
+  m.repart_time_ns = ns_since(t0);
 
-  auto t1 = std::chrono::steady_clock::now();
+  auto t1 = Clock::now();
   std::vector<std::vector<EncBatch>> parts;
   std::vector<DBufPtr> keepalive;
   build_repartition_batches(t, kparts, batch_size, offsets_host, idx,
@@ -2504,33 +2570,17 @@ static void exec_sort_shuffle_write(const Value& root, const Value& plan_doc,
                             &keepalive);
 
   // {work_dir}/{job}/{stage}/{task}/data.arrow (+.index)
-  std::string dir = plan_doc.get_str("work_dir") + "/" +
-                    plan_doc.get_str("job_id") + "/" +
-                    std::to_string(plan_doc.get_int("stage_id")) + "/" +
-                    std::to_string(plan_doc.get_int("task_id"));
-  mkdirs(dir);
-  std::string data_path = dir + "/data.arrow";
+  std::string data_path =
+      task_dir(plan_doc, plan_doc.get_int("task_id")) + "/data.arrow";
   std::vector<WriteStats> stats;
   write_consolidated(data_path, data_path + ".index", schema_msg, parts,
-                     &stats, nullptr);
-  m.write_time_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(
-                        std::chrono::steady_clock::now() - t1)
-                        .count();
+                     &stats);
+  m.write_time_ns = ns_since(t1);
   int64_t total_rows = 0;
   res.raw("\"partitions\":[");
   for (size_t p = 0; p < stats.size(); ++p) {
     if (p) res.raw(",");
-    res.raw("{\"partition_id\":");
-    res.num((int64_t)p);
-    res.raw(",\"path\":");
-    res.str(data_path);
-    res.raw(",\"num_batches\":");
-    res.num(stats[p].num_batches);
-    res.raw(",\"num_rows\":");
-    res.num(stats[p].num_rows);
-    res.raw(",\"num_bytes\":");
-    res.num(stats[p].num_bytes);
-    res.raw("}");
+    emit_partition_json(res, (int64_t)p, data_path, stats[p]);
     total_rows += stats[p].num_rows;
   }
   res.raw("]");
@@ -2546,11 +2596,11 @@ static void exec_passthrough_write(const Value& root, const Value& plan_doc,
   auto schema_msg = hex_decode(plan_doc.get_str("schema_msg_hex"));
   int64_t gp = root.get_int("global_partition");
 
-  auto t1 = std::chrono::steady_clock::now();
+  auto t1 = Clock::now();
   // identity layout: batches are row slices — no permutation, but
   // validity/offsets still need batch-aligned forms; reuse the repartition
   // batch builder with a single identity "partition"
-  DBufPtr idx = dalloc((uint64_t)(t.n > 0 ? t.n : 1) * 4);
+  DBufPtr idx = dalloc_elems(t.n, 4);
   {
     // identity permutation (for bit-gather only when any column nullable)
     std::vector<uint32_t> h((size_t)t.n);
@@ -2559,7 +2609,6 @@ static void exec_passthrough_write(const Value& root, const Value& plan_doc,
                  "bg_memcpy_h2d");
   }
   std::vector<int> fixed_ids;
-  std::vector<DBufPtr> fixed_own;  // none: slices reference t's buffers
   std::vector<DBufPtr> fixed_out;
   std::map<int, std::tuple<DBufPtr, DBufPtr, int64_t>> utf8_out;
   for (size_t c = 0; c < t.cols.size(); ++c) {
@@ -2574,8 +2623,7 @@ static void exec_passthrough_write(const Value& root, const Value& plan_doc,
       }
       if (t.cols[c].data) od = t.cols[c].data;
       else {
-        od = dalloc((uint64_t)(t.cols[c].data_bytes
-                                   ? t.cols[c].data_bytes : 1));
+        od = dalloc_elems(t.cols[c].data_bytes);
         chk(bg_memcpy_dtod(od->p, t.cols[c].dptr(),
                            (uint64_t)t.cols[c].data_bytes),
             "bg_memcpy_dtod");
@@ -2586,7 +2634,7 @@ static void exec_passthrough_write(const Value& root, const Value& plan_doc,
       if (t.cols[c].data) fixed_out.push_back(t.cols[c].data);
       else {
         int64_t esz = dt_size(t.cols[c].dtype);
-        DBufPtr b = dalloc((uint64_t)(t.n > 0 ? t.n : 1) * (uint64_t)esz);
+        DBufPtr b = dalloc_elems(t.n, esz);
         chk(bg_memcpy_dtod(b->p, t.cols[c].dptr(),
                            (uint64_t)t.n * (uint64_t)esz),
             "bg_memcpy_dtod");
@@ -2600,32 +2648,115 @@ static void exec_passthrough_write(const Value& root, const Value& plan_doc,
   build_repartition_batches(t, 1, batch_size, offsets_host, idx, fixed_out,
                             fixed_ids, utf8_out, &parts, &keepalive);
 
-  std::string dir = plan_doc.get_str("work_dir") + "/" +
-                    plan_doc.get_str("job_id") + "/" +
-                    std::to_string(plan_doc.get_int("stage_id")) + "/" +
-                    std::to_string(gp);
-  mkdirs(dir);
-  std::string data_path = dir + "/data-" +
+  std::string data_path = task_dir(plan_doc, gp) + "/data-" +
                           std::to_string(plan_doc.get_int("task_id")) +
                           ".arrow";
   std::vector<WriteStats> stats;
-  write_consolidated(data_path, "", schema_msg, parts, &stats, nullptr,
+  write_consolidated(data_path, "", schema_msg, parts, &stats,
                      /*leading_schema_stream=*/false, /*always_stream=*/true);
-  m.write_time_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(
-                        std::chrono::steady_clock::now() - t1)
-                        .count();
-  res.raw("\"partitions\":[{\"partition_id\":");
-  res.num(gp);
-  res.raw(",\"path\":");
-  res.str(data_path);
-  res.raw(",\"num_batches\":");
-  res.num(stats[0].num_batches);
-  res.raw(",\"num_rows\":");
-  res.num(stats[0].num_rows);
-  res.raw(",\"num_bytes\":");
-  res.num(stats[0].num_bytes);
-  res.raw("}]");
+  m.write_time_ns = ns_since(t1);
+  res.raw("\"partitions\":[");
+  emit_partition_json(res, gp, data_path, stats[0]);
+  res.raw("]");
   m.output_rows = stats[0].num_rows;
+}
+
+// the first nrows rows of a column, downloaded
+struct HostCol {
+  std::vector<uint8_t> data, valid;
+  std::vector<int32_t> offs;
+  std::vector<uint8_t> strdata;
+};
+
+static HostCol download_col(const Col& col, int64_t nrows) {
+  HostCol hc;
+  if (col.dtype == BG_DT_UTF8) {
+    hc.offs.resize((size_t)nrows + 1);
+    if (nrows)
+      chk(bg_memcpy_d2h(hc.offs.data(), col.optr(), (uint64_t)(nrows + 1) * 4),
+          "bg_memcpy_d2h");
+    else hc.offs = {0};
+    int64_t nb = hc.offs[(size_t)nrows] - hc.offs[0];
+    hc.strdata.resize((size_t)(nb > 0 ? nb : 0));
+    if (nb)
+      chk(bg_memcpy_d2h(hc.strdata.data(),
+                        (const uint8_t*)col.dptr() + hc.offs[0], (uint64_t)nb),
+          "bg_memcpy_d2h");
+  } else {
+    int64_t esz = dt_size(col.dtype);
+    hc.data.resize((size_t)(nrows * esz));
+    if (nrows)
+      chk(bg_memcpy_d2h(hc.data.data(), col.dptr(), (uint64_t)(nrows * esz)),
+          "bg_memcpy_d2h");
+  }
+  if (col.nullable()) {
+    hc.valid.resize((size_t)((nrows + 7) / 8) + 8);
+    if (nrows)
+      chk(bg_memcpy_d2h(hc.valid.data(), col.vptr(),
+                        (uint64_t)((nrows + 7) / 8)),
+          "bg_memcpy_d2h");
+  }
+  return hc;
+}
+
+// row r of a column as a JSON value
+static void emit_cell(bgjson::Writer& res, int32_t dtype, const HostCol& hc,
+                      int64_t r) {
+  if (!hc.valid.empty() && !((hc.valid[(size_t)(r >> 3)] >> (r & 7)) & 1)) {
+    res.raw("null");
+    return;
+  }
+  switch (dtype) {
+    case BG_DT_INT32:
+    case BG_DT_DATE32: {
+      int32_t v;
+      memcpy(&v, hc.data.data() + r * 4, 4);
+      res.num(v);
+      break;
+    }
+    case BG_DT_DICT8: res.num(hc.data[(size_t)r]); break;
+    case BG_DT_INT64: {
+      int64_t v;
+      memcpy(&v, hc.data.data() + r * 8, 8);
+      res.num(v);
+      break;
+    }
+    case BG_DT_FLOAT64: {
+      double v;
+      memcpy(&v, hc.data.data() + r * 8, 8);
+      res.dbl(v);
+      break;
+    }
+    case BG_DT_DECIMAL128: {
+      unsigned __int128 u = 0;
+      memcpy(&u, hc.data.data() + r * 16, 16);
+      __int128 v = (__int128)u;
+      // decimal integer string (scaled); host formats with scale
+      char buf[48];
+      int pos = 47;
+      buf[pos] = '\0';
+      bool neg = v < 0;
+      unsigned __int128 uv = neg ? (unsigned __int128)(-v)
+                                 : (unsigned __int128)v;
+      if (uv == 0) buf[--pos] = '0';
+      while (uv) {
+        buf[--pos] = (char)('0' + (int)(uv % 10));
+        uv /= 10;
+      }
+      if (neg) buf[--pos] = '-';
+      res.raw("\"");
+      res.raw(buf + pos);
+      res.raw("\"");
+      break;
+    }
+    case BG_DT_UTF8: {
+      int32_t lo = hc.offs[(size_t)r] - hc.offs[0];
+      int32_t hi = hc.offs[(size_t)r + 1] - hc.offs[0];
+      res.str(std::string((const char*)hc.strdata.data() + lo,
+                          (size_t)(hi - lo)));
+      break;
+    }
+  }
 }
 
 // collect root: download and serialise rows (final stages / tests)
@@ -2653,108 +2784,14 @@ static void exec_collect(const Value& root, Metrics& m, bgjson::Writer& res) {
   }
   res.raw("],\"rows\":[");
 
-  // download columns
-  struct HostCol {
-    std::vector<uint8_t> data, valid;
-    std::vector<int32_t> offs;
-    std::vector<uint8_t> strdata;
-  };
-  std::vector<HostCol> host(t.cols.size());
-  for (size_t c = 0; c < t.cols.size(); ++c) {
-    auto& hc = host[c];
-    const Col& col = t.cols[c];
-    if (col.dtype == BG_DT_UTF8) {
-      hc.offs.resize((size_t)nrows + 1);
-      if (nrows)
-        chk(bg_memcpy_d2h(hc.offs.data(), col.optr(),
-                          (uint64_t)(nrows + 1) * 4),
-            "bg_memcpy_d2h");
-      else hc.offs = {0};
-      int64_t nb = hc.offs[(size_t)nrows] - hc.offs[0];
-      hc.strdata.resize((size_t)(nb > 0 ? nb : 0));
-      if (nb)
-        chk(bg_memcpy_d2h(hc.strdata.data(),
-                          (const uint8_t*)col.dptr() + hc.offs[0],
-                          (uint64_t)nb),
-            "bg_memcpy_d2h");
-    } else {
-      int64_t esz = dt_size(col.dtype);
-      hc.data.resize((size_t)(nrows * esz));
-      if (nrows)
-        chk(bg_memcpy_d2h(hc.data.data(), col.dptr(),
-                          (uint64_t)(nrows * esz)),
-            "bg_memcpy_d2h");
-    }
-    if (col.nullable()) {
-      hc.valid.resize((size_t)((nrows + 7) / 8) + 8);
-      if (nrows)
-        chk(bg_memcpy_d2h(hc.valid.data(), col.vptr(),
-                          (uint64_t)((nrows + 7) / 8)),
-            "bg_memcpy_d2h");
-    }
-  }
+  std::vector<HostCol> host;
+  for (auto& col : t.cols) host.push_back(download_col(col, nrows));
   for (int64_t r = 0; r < nrows; ++r) {
     if (r) res.raw(",");
     res.raw("[");
     for (size_t c = 0; c < t.cols.size(); ++c) {
       if (c) res.raw(",");
-      auto& hc = host[c];
-      const Col& col = t.cols[c];
-      if (!hc.valid.empty() && !((hc.valid[(size_t)(r >> 3)] >> (r & 7)) & 1)) {
-        res.raw("null");
-        continue;
-      }
-      switch (col.dtype) {
-        case BG_DT_INT32:
-        case BG_DT_DATE32: {
-          int32_t v;
-          memcpy(&v, hc.data.data() + r * 4, 4);
-          res.num(v);
-          break;
-        }
-        case BG_DT_DICT8: res.num(hc.data[(size_t)r]); break;
-        case BG_DT_INT64: {
-          int64_t v;
-          memcpy(&v, hc.data.data() + r * 8, 8);
-          res.num(v);
-          break;
-        }
-        case BG_DT_FLOAT64: {
-          double v;
-          memcpy(&v, hc.data.data() + r * 8, 8);
-          res.dbl(v);
-          break;
-        }
-        case BG_DT_DECIMAL128: {
-          unsigned __int128 u = 0;
-          memcpy(&u, hc.data.data() + r * 16, 16);
-          __int128 v = (__int128)u;
-          // decimal integer string (scaled); host formats with scale
-          char buf[48];
-          int pos = 47;
-          buf[pos] = '\0';
-          bool neg = v < 0;
-          unsigned __int128 uv = neg ? (unsigned __int128)(-v)
-                                     : (unsigned __int128)v;
-          if (uv == 0) buf[--pos] = '0';
-          while (uv) {
-            buf[--pos] = (char)('0' + (int)(uv % 10));
-            uv /= 10;
-          }
-          if (neg) buf[--pos] = '-';
-          res.raw("\"");
-          res.raw(buf + pos);
-          res.raw("\"");
-          break;
-        }
-        case BG_DT_UTF8: {
-          int32_t lo = hc.offs[(size_t)r] - hc.offs[0];
-          int32_t hi = hc.offs[(size_t)r + 1] - hc.offs[0];
-          res.str(std::string((const char*)hc.strdata.data() + lo,
-                              (size_t)(hi - lo)));
-          break;
-        }
-      }
+      emit_cell(res, t.cols[c].dtype, host[c], r);
     }
     res.raw("]");
   }
@@ -2829,27 +2866,18 @@ static VSchema validate_plan(const Value& node) {
     VSchema p = validate_plan(node.at("probe"));
     for (auto& k : node.get_arr("build_keys")) b.idx(k->s);
     for (auto& k : node.get_arr("probe_keys")) p.idx(k->s);
-    const std::string jt = node.get_str_or("join_type", "inner");
-    if (jt != "inner" && jt != "semi" && jt != "anti" && jt != "left" &&
-        jt != "semi_build" && jt != "anti_build" && jt != "outer_build" &&
-        jt != "full")
-      throw StageError(BG_ERR_UNSUPPORTED, "hash_join: join_type " + jt);
-    const bool build_rows_only = jt == "semi_build" || jt == "anti_build";
+    const JoinKind& k = join_kind(node);
     VSchema out;
-    for (auto& o : node.get_arr("output")) {
-      if (build_rows_only) require_build_side(jt, *o);
-      const VSchema& src = o->get_str("side") == "build" ? b : p;
-      int i = src.idx(o->get_str("col"));
-      out.names.push_back(o->get_str_or("as", o->get_str("col")));
-      out.dts.push_back(src.dts[(size_t)i]);
+    for (auto& ov : node.get_arr("output")) {
+      const JoinOut o = join_output(k, *ov);
+      const VSchema& src = o.build ? b : p;
+      out.dts.push_back(src.dts[(size_t)src.idx(o.col)]);
+      out.names.push_back(o.as);
     }
     return out;
   }
   if (op == "hash_aggregate") {
-    const Value& child = node.at("input");
-    VSchema in = child.get_str("op") == "filter"
-                     ? validate_plan(child)
-                     : validate_plan(child);
+    VSchema in = validate_plan(node.at("input"));
     const std::string mode = node.get_str_or("mode", "single");
     VSchema out;
     for (auto& k : node.get_arr("group_by")) {
@@ -2860,52 +2888,18 @@ static VSchema validate_plan(const Value& node) {
     for (auto& a : node.get_arr("aggs")) {
       const std::string fn = a->get_str("fn");
       const std::string as = a->get_str("as");
-      if (fn != "sum" && fn != "min" && fn != "max" && fn != "count" &&
-          fn != "avg")
-        throw StageError(BG_ERR_INVALID, "aggregate fn " + fn);
-      DtSpec dt{BG_DT_INT64, 0, 0};
+      check_agg_fn(fn);
+      DtSpec src = DT_I64;  // the aggregate's input dtype (count: unused)
       if (mode == "final") {
-        if (fn == "avg") {
-          in.idx(as + "$s");
-          in.idx(as + "$n");
-          DtSpec sdt = in.dts[(size_t)in.idx(as + "$s")];
-          dt = sdt.dt == BG_DT_FLOAT64
-                   ? DtSpec{BG_DT_FLOAT64, 0, 0}
-                   : DtSpec{BG_DT_DECIMAL128,
-                            sdt.precision + 4 > 38 ? 38 : sdt.precision + 4,
-                            sdt.scale + 4};
-        } else if (fn != "count") {
-          in.idx(as + "$n");
-          dt = in.dts[(size_t)in.idx(as)];
-        }
+        auto partial = agg_partial_names(fn, as);
+        for (auto& name : partial) in.idx(name);
+        src = in.dts[(size_t)in.idx(partial[0])];
       } else if (fn != "count" || a->has("expr")) {
-        dt = validate_expr(in, a->at("expr"));
-        if (fn == "avg")
-          dt = dt.dt == BG_DT_FLOAT64
-                   ? DtSpec{BG_DT_FLOAT64, 0, 0}
-                   : DtSpec{BG_DT_DECIMAL128,
-                            dt.precision + 4 > 38 ? 38 : dt.precision + 4,
-                            dt.scale + 4};
+        src = validate_expr(in, a->at("expr"));
       }
-      if (fn == "count") dt = {BG_DT_INT64, 0, 0};
-      if (mode == "partial") {
-        if (fn == "avg") {
-          out.names.push_back(as + "$s");
-          out.dts.push_back(validate_expr(in, a->at("expr")));
-          out.names.push_back(as + "$n");
-          out.dts.push_back({BG_DT_INT64, 0, 0});
-        } else if (fn == "count") {
-          out.names.push_back(as);
-          out.dts.push_back({BG_DT_INT64, 0, 0});
-        } else {
-          out.names.push_back(as);
-          out.dts.push_back(dt);
-          out.names.push_back(as + "$n");
-          out.dts.push_back({BG_DT_INT64, 0, 0});
-        }
-      } else {
-        out.names.push_back(as);
-        out.dts.push_back(dt);
+      for (auto& f : agg_output_fields(fn, mode, as, src)) {
+        out.names.push_back(f.name);
+        out.dts.push_back(f.dt);
       }
     }
     return out;
@@ -3022,7 +3016,7 @@ extern "C" int bg_execute_stage(const char* plan_json, char** out_json) {
     ValuePtr doc = parser.parse();
     (void)validate_root(*doc);  // fail fast with a typed message
 
-    auto t0 = std::chrono::steady_clock::now();
+    auto t0 = Clock::now();
     Metrics m;
     bgjson::Writer res;
     res.raw("{");
@@ -3035,9 +3029,7 @@ extern "C" int bg_execute_stage(const char* plan_json, char** out_json) {
     else
       exec_collect(root, m, res);
     chk(bg_synchronize(), "bg_synchronize");
-    int64_t total_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(
-                           std::chrono::steady_clock::now() - t0)
-                           .count();
+    int64_t total_ns = ns_since(t0);
     // metric names mirror the reference writer's MetricsSet
     // (sort_shuffle/writer.rs:328-440) + the GPU counters of SURVEY.md §5
     res.raw(",\"metrics\":{\"repart_time_ns\":");
@@ -3071,10 +3063,7 @@ extern "C" int bg_stage_register_table(const char* name,
     Table t;
     t.n = n_rows;
     for (int32_t c = 0; c < ncols; ++c) {
-      Col col;
-      col.dtype = cols[c].dtype;
-      col.precision = cols[c].precision;
-      col.scale = cols[c].scale;
+      Col col = make_col({cols[c].dtype, cols[c].precision, cols[c].scale});
       col.ext_data = cols[c].d_data;
       col.ext_valid = cols[c].d_validity;
       col.ext_offs = cols[c].d_offsets;

@@ -98,6 +98,55 @@ def test_validate_aggregate_modes():
     assert [f["name"] for f in res["schema"]] == ["k", "s", "c", "a"]
 
 
+_AGG_IN = {
+    "int64": {"dtype": "int64"},
+    "decimal128": {"dtype": "decimal128", "precision": 15, "scale": 2},
+    "float64": {"dtype": "float64"},
+}
+
+
+def _agg_expected(fn, mode, in_dtype):
+    """The aggregate output rules, written out by hand: a count is one
+    int64 column in every mode; partial mode emits the value (avg: the
+    running sum as "$s") plus an int64 "$n" non-null count; sum/min/max
+    keep the input dtype; avg gives float64 for float64 and decimal128
+    for everything else."""
+    if fn in ("count", "count(*)"):
+        return [("a", "int64")]
+    if mode == "partial":
+        return [("a$s" if fn == "avg" else "a", in_dtype), ("a$n", "int64")]
+    if fn == "avg":
+        return [("a", "float64" if in_dtype == "float64" else "decimal128")]
+    return [("a", in_dtype)]
+
+
+@pytest.mark.parametrize("in_dtype", ["int64", "decimal128", "float64"])
+@pytest.mark.parametrize("mode", ["single", "partial", "final"])
+@pytest.mark.parametrize("fn", ["sum", "min", "max", "count", "count(*)",
+                                "avg"])
+def test_validate_aggregate_output_fields(fn, mode, in_dtype):
+    agg = {"fn": "count" if fn == "count(*)" else fn, "as": "a"}
+    if mode == "final":
+        # final reads the partial columns by name
+        if agg["fn"] == "count":
+            fields = [dict(name="a", dtype="int64")]
+        else:
+            fields = [dict(_AGG_IN[in_dtype],
+                           name="a$s" if fn == "avg" else "a"),
+                      dict(name="a$n", dtype="int64")]
+    else:
+        fields = [dict(_AGG_IN[in_dtype], name="v")]
+        if fn != "count(*)":
+            agg["expr"] = {"col": "v"}
+    schema = [{"name": "k", "dtype": "int64"}] + fields
+    plan = {"op": "collect", "input": {
+        "op": "hash_aggregate", "mode": mode, "group_by": ["k"],
+        "aggs": [agg], "input": _scan("t", schema)}}
+    res = stage.validate(_doc(plan))
+    got = [(f["name"], f["dtype"]) for f in res["schema"]]
+    assert got == [("k", "int64")] + _agg_expected(fn, mode, in_dtype)
+
+
 def test_validate_sort_shuffle_write_requires_schema_msg():
     plan = {"op": "sort_shuffle_write", "k": 16,
             "keys": [{"col": "k"}], "input": _scan()}
