@@ -57,7 +57,7 @@ static thread_local bool g_inited = false;
 static thread_local double g_last_kernel_ms = 0.0;
 
 extern "C" const char* bg_last_error(void) { return g_err; }
-extern "C" int bg_version(void) { return 11; }
+extern "C" int bg_version(void) { return 12; }
 
 // Build provenance: the sha256 over the library's seven sources
 // (kernels.hip, bg_ahash.h, stage.cpp, stage_ipc.h, stage_json.h,
@@ -7349,6 +7349,342 @@ extern "C" int bg_bitmap_or(const uint8_t* d_a, const uint8_t* d_b,
       (int)bg_imin64((nbytes + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
   hipLaunchKernelGGL(k_bitmap_or, dim3(blocks), dim3(BG_BLOCK), 0, 0, d_a,
                      d_b, nbytes, d_out);
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Scalar expressions of the approved plans that are neither Decimal128
+// arithmetic nor a column-vs-literal predicate: date_part (q7/q8/q9),
+// substr and Utf8 IN-lists (q22), column-vs-column compares (q4/q12/q21).
+// ---------------------------------------------------------------------------
+
+// One Date32 day number -> one date part, proleptic Gregorian, exact for
+// EVERY int32 input in 32-bit arithmetic.  The civil-from-days chain wants
+// z + 719468 (days since 0000-03-01) floor-divided by the 146097-day era;
+// with u = z + 2^31 (u32, a sign-bit flip) that is
+//   z + 719468 = (u - 14862) - 14694 * 146097,
+// so u - 14862 divides unsigned.  Only the lowest 14862 inputs would wrap:
+// they take one era more (u + 131235 < 146097) and era - 1 instead.  No
+// signed value ever leaves [-5.9M, 5.9M]; every division is u32 by a
+// constant.
+template <int PART>
+__device__ __forceinline__ int32_t date_part_one(int32_t z) {
+  const uint32_t u = (uint32_t)z ^ 0x80000000u;
+  if (PART == BG_DATE_PART_DOW) {
+    // 1970-01-01 is a Thursday (4) and 2^31 mod 7 == 2: dow = (u - 2 + 4) % 7
+    const uint32_t r = u % 7u + 2u;
+    return (int32_t)(r >= 7u ? r - 7u : r);
+  }
+  const bool low = u < 14862u;
+  const uint32_t v = low ? u + 131235u : u - 14862u;
+  const uint32_t e = v / 146097u;
+  const uint32_t doe = v - e * 146097u;                          // [0, 146096]
+  const uint32_t yoe =
+      (doe - doe / 1460u + doe / 36524u - doe / 146096u) / 365u; // [0, 399]
+  const uint32_t doy =
+      doe - (365u * yoe + yoe / 4u - yoe / 100u);                // [0, 365]
+  const uint32_t mp = (5u * doy + 2u) / 153u;                    // [0, 11]
+  const bool jan_feb = mp >= 10u;  // the March-based year's last two months
+  if (PART == BG_DATE_PART_DAY)
+    return (int32_t)(doy - (153u * mp + 2u) / 5u + 1u);
+  if (PART == BG_DATE_PART_DOY) {
+    if (jan_feb) return (int32_t)(doy - 305u);  // Jan 1 is March-based day 306
+    const bool leap = (yoe & 3u) == 0u && (yoe % 100u != 0u || yoe == 0u);
+    return (int32_t)(doy + 60u + (leap ? 1u : 0u));
+  }
+  const uint32_t m = jan_feb ? mp - 9u : mp + 3u;                // [1, 12]
+  if (PART == BG_DATE_PART_MONTH) return (int32_t)m;
+  if (PART == BG_DATE_PART_QUARTER) return (int32_t)((m + 2u) / 3u);
+  const int32_t era = (int32_t)e - (low ? 14695 : 14694);
+  return (int32_t)yoe + era * 400 + (jan_feb ? 1 : 0);
+}
+
+// streaming: 4 B in, 4 B out per row; four rows per lane through 16-byte
+// non-temporal accesses (nvec of them), scalar tail for the last n % 4
+template <int PART>
+__global__ __launch_bounds__(BG_BLOCK) void k_date_part(
+    const int32_t* __restrict__ in, int64_t n, int64_t nvec,
+    int32_t* __restrict__ out) {
+  typedef int i32x4_dp __attribute__((ext_vector_type(4)));
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t v = tid; v < nvec; v += stride) {
+    const i32x4_dp x = __builtin_nontemporal_load(
+        reinterpret_cast<const i32x4_dp*>(in) + v);
+    i32x4_dp r;
+    r[0] = date_part_one<PART>(x[0]);
+    r[1] = date_part_one<PART>(x[1]);
+    r[2] = date_part_one<PART>(x[2]);
+    r[3] = date_part_one<PART>(x[3]);
+    __builtin_nontemporal_store(r, reinterpret_cast<i32x4_dp*>(out) + v);
+  }
+  for (int64_t i = nvec * 4 + tid; i < n; i += stride)
+    out[i] = date_part_one<PART>(in[i]);
+}
+
+template <int PART>
+static void launch_date_part(const int32_t* in, int64_t n, int32_t* out) {
+  // the 16-byte path needs both pointers 16-byte aligned (sliced columns
+  // may not be); otherwise every row takes the scalar loop
+  const bool aligned = (((uintptr_t)in | (uintptr_t)out) & 15u) == 0;
+  const int64_t nvec = aligned ? n / 4 : 0;
+  const int blocks = grid_for(nvec > 0 ? nvec : n);
+  hipLaunchKernelGGL(k_date_part<PART>, dim3(blocks), dim3(BG_BLOCK), 0, 0, in,
+                     n, nvec, out);
+}
+
+extern "C" int bg_date_part(const bg_column* col, int32_t part, int64_t n,
+                            int32_t* d_out) {
+  REQUIRE_INIT();
+  if (col->dtype != BG_DT_DATE32)
+    return set_err(BG_ERR_INVALID, "bg_date_part: Date32 column required");
+  if (n < 0) return set_err(BG_ERR_INVALID, "bg_date_part: negative n");
+  const int32_t* in = (const int32_t*)col->d_data;
+  switch (part) {
+    case BG_DATE_PART_YEAR:
+      launch_date_part<BG_DATE_PART_YEAR>(in, n, d_out); break;
+    case BG_DATE_PART_QUARTER:
+      launch_date_part<BG_DATE_PART_QUARTER>(in, n, d_out); break;
+    case BG_DATE_PART_MONTH:
+      launch_date_part<BG_DATE_PART_MONTH>(in, n, d_out); break;
+    case BG_DATE_PART_DAY:
+      launch_date_part<BG_DATE_PART_DAY>(in, n, d_out); break;
+    case BG_DATE_PART_DOY:
+      launch_date_part<BG_DATE_PART_DOY>(in, n, d_out); break;
+    case BG_DATE_PART_DOW:
+      launch_date_part<BG_DATE_PART_DOW>(in, n, d_out); break;
+    default:
+      return set_err(BG_ERR_UNSUPPORTED,
+                     "bg_date_part: part must be year/quarter/month/day/"
+                     "doy/dow");
+  }
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+// substr bounds pass, one lane per row: walk the row's bytes counting
+// code-point starts until code point `e` is reached, remembering where code
+// point `s` began.  Emits the slice's byte length and source address — the
+// (lens, srcaddr) pair bg_ba_materialize lays out and copies.  s >= 0 and e
+// arrive clamped/saturated from the host; NULL rows emit zero bytes and
+// read no payload.
+__global__ void k_substr_bounds(const uint8_t* __restrict__ data,
+                                const int32_t* __restrict__ offs,
+                                const uint8_t* __restrict__ valid, int64_t s,
+                                int64_t e, int64_t n,
+                                int64_t* __restrict__ lens,
+                                int64_t* __restrict__ srcaddr) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t len = 0;
+    const uint8_t* src = nullptr;
+    if (e > s && bit_valid(valid, i)) {
+      const int32_t lo = offs[i], hi = offs[i + 1];
+      int32_t bs = hi, be = hi;  // row shorter than s / e code points
+      int64_t cp = 0;
+      for (int32_t b = lo; b < hi; ++b) {
+        if ((data[b] & 0xC0) == 0x80) continue;  // continuation byte
+        if (cp == s) bs = b;
+        if (cp == e) { be = b; break; }
+        ++cp;
+      }
+      len = be - bs;
+      if (len > 0) src = data + bs;
+    }
+    lens[i] = len;
+    srcaddr[i] = (int64_t)(uintptr_t)src;
+  }
+}
+
+extern "C" int bg_substr(const bg_column* col, int64_t start,
+                         int32_t has_count, int64_t count, int64_t n,
+                         int32_t* d_out_offsets, void* d_out_data,
+                         int64_t out_data_cap, int64_t* out_total_bytes) {
+  REQUIRE_INIT();
+  if (col->dtype != BG_DT_UTF8 || !col->d_offsets)
+    return set_err(BG_ERR_INVALID, "bg_substr: Utf8 column required");
+  if (has_count && count < 0)
+    return set_err(BG_ERR_INVALID,
+                   "bg_substr: negative substring length not allowed");
+  if (n < 0) return set_err(BG_ERR_INVALID, "bg_substr: negative n");
+  // code points [max(s, 0), e) with s = start - 1, e = s + count; both
+  // saturate instead of wrapping (a row never holds 2^63 code points)
+  const int64_t s0 = start == INT64_MIN ? INT64_MIN : start - 1;
+  int64_t e = INT64_MAX;  // no count: to the end of the row
+  if (has_count && __builtin_add_overflow(s0, count, &e))
+    e = INT64_MAX;  // count >= 0: the sum can only overflow upwards
+  const int64_t s = s0 < 0 ? 0 : s0;
+  DevBuf<int64_t> d_lens;
+  DevBuf<int64_t> d_srcaddr;
+  HIP_TRY(d_lens.alloc(n));
+  HIP_TRY(d_srcaddr.alloc(n));
+  hipLaunchKernelGGL(k_substr_bounds, dim3(grid_for(n)), dim3(BG_BLOCK), 0, 0,
+                     (const uint8_t*)col->d_data, col->d_offsets,
+                     col->d_validity, s, e, n, d_lens.get(), d_srcaddr.get());
+  HIP_TRY(hipGetLastError());
+  // layout + copy (and the d_out_data == NULL sizing convention) are
+  // bg_ba_materialize's
+  int rc = bg_ba_materialize(d_lens, d_srcaddr, n, d_out_offsets,
+                             (uint8_t*)d_out_data, out_data_cap,
+                             out_total_bytes);
+  if (rc != BG_OK) return rc;
+  if (*out_total_bytes > 0x7fffffffLL)
+    return set_err(BG_ERR_INVALID, "bg_substr: >2GiB Utf8 result");
+  return BG_OK;
+}
+
+// Column-vs-column compare (q4/q12/q21: l_receiptdate > l_commitdate,
+// l_shipdate < l_commitdate).  As k_eval_predicates, one wave per 64 rows
+// and ballot word == bitmap word, but it reads the mask word FIRST: a wave
+// whose word is already zero loads neither column (after q12's literal date
+// window about one row in seven is left), and a lane whose bit is clear
+// loads nothing.  Stores old & ballot; rows >= n never vote, so the last
+// word's tail bits come out 0.
+template <typename T>
+__device__ __forceinline__ T cmp_load(const void* base, int64_t row) {
+  return __builtin_nontemporal_load(reinterpret_cast<const T*>(base) + row);
+}
+// Decimal128 as signed i128: high word signed, low word unsigned
+template <>
+__device__ __forceinline__ i128 cmp_load<i128>(const void* base, int64_t row) {
+  typedef unsigned long long ull2_cc __attribute__((ext_vector_type(2)));
+  const ull2_cc v = __builtin_nontemporal_load(
+      reinterpret_cast<const ull2_cc*>(base) + row);
+  return make_i128(v[0], (i64)v[1]);
+}
+
+template <typename T>
+__global__ void k_eval_compare_cols(const void* __restrict__ a,
+                                    const uint8_t* __restrict__ avalid,
+                                    const void* __restrict__ b,
+                                    const uint8_t* __restrict__ bvalid,
+                                    int cmp, int64_t n, u64* mask_words,
+                                    int64_t nwords) {
+  const int64_t wave_global =
+      ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / BG_WAVE;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) / BG_WAVE;
+  const int lane = lane_id();
+  for (int64_t w = wave_global; w < nwords; w += nwaves) {
+    const u64 old = mask_words[w];
+    if (old == 0) continue;  // wave-uniform: nothing left to decide
+    const int64_t row = w * BG_WAVE + lane;
+    bool keep = row < n && ((old >> lane) & 1) && bit_valid(avalid, row) &&
+                bit_valid(bvalid, row);
+    if (keep) {
+      const T x = cmp_load<T>(a, row), y = cmp_load<T>(b, row);
+      switch (cmp) {
+        case BG_CMP_LT: keep = x < y; break;
+        case BG_CMP_LE: keep = x <= y; break;
+        case BG_CMP_GT: keep = x > y; break;
+        case BG_CMP_GE: keep = x >= y; break;
+        case BG_CMP_EQ: keep = x == y; break;
+        default: keep = x != y; break;  // BG_CMP_NE (host checked the range)
+      }
+    }
+    const u64 m = __ballot(keep);
+    if (lane == 0) mask_words[w] = old & m;
+  }
+}
+
+extern "C" int bg_eval_compare_cols(const bg_column* a, const bg_column* b,
+                                    int32_t cmp, int64_t n, uint8_t* d_mask) {
+  REQUIRE_INIT();
+  if (cmp < BG_CMP_LT || cmp > BG_CMP_NE)
+    return set_err(BG_ERR_INVALID, "bg_eval_compare_cols: unknown cmp");
+  if (a->dtype == BG_DT_FLOAT64 || a->dtype == BG_DT_UTF8 ||
+      b->dtype == BG_DT_FLOAT64 || b->dtype == BG_DT_UTF8)
+    return set_err(BG_ERR_UNSUPPORTED,
+                   "bg_eval_compare_cols: Float64/Utf8 columns");
+  if (a->dtype != b->dtype)
+    return set_err(BG_ERR_INVALID, "bg_eval_compare_cols: dtype mismatch");
+  if (a->dtype == BG_DT_DECIMAL128 && a->scale != b->scale)
+    return set_err(BG_ERR_INVALID,
+                   "bg_eval_compare_cols: Decimal128 scale mismatch");
+  if (n < 0) return set_err(BG_ERR_INVALID, "bg_eval_compare_cols: negative n");
+  const int64_t nwords = (n + 63) / 64;
+  const int blocks = grid_for(nwords * BG_WAVE);
+#define BG_LAUNCH_CMP(T)                                                      \
+  hipLaunchKernelGGL(k_eval_compare_cols<T>, dim3(blocks), dim3(BG_BLOCK), 0, \
+                     0, a->d_data, a->d_validity, b->d_data, b->d_validity,   \
+                     cmp, n, (u64*)d_mask, nwords)
+  switch (a->dtype) {
+    case BG_DT_INT32:
+    case BG_DT_DATE32: BG_LAUNCH_CMP(int32_t); break;
+    case BG_DT_INT64: BG_LAUNCH_CMP(int64_t); break;
+    case BG_DT_DICT8: BG_LAUNCH_CMP(uint8_t); break;
+    case BG_DT_DECIMAL128: BG_LAUNCH_CMP(i128); break;
+    default:
+      return set_err(BG_ERR_INVALID, "bg_eval_compare_cols: unknown dtype");
+  }
+#undef BG_LAUNCH_CMP
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+// Utf8 IN-list (q22: substr(c_phone, 1, 2) IN ('13', '31', ...)): exact
+// byte equality against up to 16 literals of up to 64 bytes, passed by
+// value like BgLikeArgs.  ANDs into the mask; NULL => false.
+#define BG_IN_UTF8_MAX_VALUES 16
+
+struct BgInUtf8Args {
+  const uint8_t* d_data;
+  const int32_t* d_offsets;
+  const uint8_t* d_validity;
+  uint8_t vals[BG_IN_UTF8_MAX_VALUES][BG_LIKE_MAX_PAT];
+  int32_t val_len[BG_IN_UTF8_MAX_VALUES];
+  int32_t nvals;
+};
+
+__global__ void k_eval_in_utf8(BgInUtf8Args a, int64_t n, u64* mask_words) {
+  const int64_t wave_global =
+      ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / BG_WAVE;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) / BG_WAVE;
+  const int lane = lane_id();
+  const int64_t nwords = (n + 63) / 64;
+  for (int64_t w = wave_global; w < nwords; w += nwaves) {
+    const int64_t i = w * BG_WAVE + lane;
+    bool hit = false;
+    if (i < n && bit_valid(a.d_validity, i)) {
+      const int32_t lo = a.d_offsets[i], len = a.d_offsets[i + 1] - lo;
+      const uint8_t* s = a.d_data + lo;
+      for (int v = 0; v < a.nvals && !hit; ++v) {
+        if (a.val_len[v] != len) continue;
+        bool eq = true;
+        for (int32_t j = 0; j < len; ++j)
+          if (s[j] != a.vals[v][j]) { eq = false; break; }
+        hit = eq;
+      }
+    }
+    const u64 m = __ballot(hit);
+    if (lane == 0) mask_words[w] &= m;
+  }
+}
+
+extern "C" int bg_eval_in_utf8(const bg_column* col, const char* const* values,
+                               const int32_t* value_lens, int32_t nvalues,
+                               int64_t n, uint8_t* d_mask) {
+  REQUIRE_INIT();
+  if (col->dtype != BG_DT_UTF8 || !col->d_offsets)
+    return set_err(BG_ERR_INVALID, "bg_eval_in_utf8: Utf8 column required");
+  if (nvalues < 1 || nvalues > BG_IN_UTF8_MAX_VALUES)
+    return set_err(BG_ERR_INVALID, "bg_eval_in_utf8: 1..16 values");
+  if (n < 0) return set_err(BG_ERR_INVALID, "bg_eval_in_utf8: negative n");
+  BgInUtf8Args a{};
+  a.d_data = (const uint8_t*)col->d_data;
+  a.d_offsets = col->d_offsets;
+  a.d_validity = col->d_validity;
+  a.nvals = nvalues;
+  for (int v = 0; v < nvalues; ++v) {
+    if (value_lens[v] <= 0 || value_lens[v] > BG_LIKE_MAX_PAT)
+      return set_err(BG_ERR_INVALID, "bg_eval_in_utf8: value length 1..64");
+    a.val_len[v] = value_lens[v];
+    memcpy(a.vals[v], values[v], (size_t)value_lens[v]);
+  }
+  const int64_t nwords = (n + 63) / 64;
+  int blocks = grid_for(nwords * BG_WAVE);
+  hipLaunchKernelGGL(k_eval_in_utf8, dim3(blocks), dim3(BG_BLOCK), 0, 0, a, n,
+                     (u64*)d_mask);
   HIP_TRY(hipGetLastError());
   return BG_OK;
 }

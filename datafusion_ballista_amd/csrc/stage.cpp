@@ -1030,6 +1030,24 @@ struct ExprVal {
 
 static ExprVal eval_expr(const Table& t, const Value& e);
 
+// date_part's "part" names (validation and execution both read this)
+static int32_t date_part_code(const std::string& s) {
+  if (s == "year") return BG_DATE_PART_YEAR;
+  if (s == "quarter") return BG_DATE_PART_QUARTER;
+  if (s == "month") return BG_DATE_PART_MONTH;
+  if (s == "day") return BG_DATE_PART_DAY;
+  if (s == "doy") return BG_DATE_PART_DOY;
+  if (s == "dow") return BG_DATE_PART_DOW;
+  throw StageError(BG_ERR_INVALID, "date_part: unknown part '" + s + "'");
+}
+
+// a unary projection's result is NULL exactly where its argument is: share
+// the argument's bitmap (owned or registered-table external)
+static void share_validity(const Col& arg, Col* out) {
+  out->validity = arg.validity;
+  out->ext_valid = arg.validity ? nullptr : arg.ext_valid;
+}
+
 static Col eval_dec_binary(const Table& t, int op_cc, int op_cl, int op_lc,
                            const Value& l, const Value& r) {
   ExprVal a = eval_expr(t, l);
@@ -1167,6 +1185,45 @@ static ExprVal eval_expr(const Table& t, const Value& e) {
                   v2.col.data->p),
         "bg_select");
     return v2;
+  }
+  // date_part(part, date32) -> int32  (q7/q8/q9: GROUP BY the year)
+  if (e.has("date_part")) {
+    const Value& d = e.at("date_part");
+    ExprVal a = eval_expr(t, d.at("arg"));
+    if (a.is_lit) throw StageError(BG_ERR_INVALID, "date_part of a literal");
+    Col out = make_col({BG_DT_INT32, 0, 0});
+    out.data = dalloc_elems(t.n, 4);
+    bg_column ba = to_bg(a.col, t.n);
+    chk(bg_date_part(&ba, date_part_code(d.get_str("part")), t.n,
+                     (int32_t*)out.data->p),
+        "bg_date_part");
+    share_validity(a.col, &out);
+    v.col = out;
+    return v;
+  }
+  // substr(utf8, start[, count]) -> utf8  (q22: the country code)
+  if (e.has("substr")) {
+    const Value& d = e.at("substr");
+    ExprVal a = eval_expr(t, d.at("arg"));
+    if (a.is_lit) throw StageError(BG_ERR_INVALID, "substr of a literal");
+    const int64_t start = d.get_int("start");
+    const bool has_count = d.has("count");
+    const int64_t count = has_count ? d.get_int("count") : 0;
+    Col out = make_col({BG_DT_UTF8, 0, 0});
+    out.offsets = dalloc((uint64_t)(t.n + 1) * 4);
+    bg_column ba = to_bg(a.col, t.n);
+    int64_t total = 0;  // size exactly first (d_out_data NULL), then copy
+    chk(bg_substr(&ba, start, has_count, count, t.n, (int32_t*)out.offsets->p,
+                  nullptr, 0, &total),
+        "bg_substr(size)");
+    out.data = dalloc_elems(total);
+    chk(bg_substr(&ba, start, has_count, count, t.n, (int32_t*)out.offsets->p,
+                  out.data->p, total > 0 ? total : 1, &total),
+        "bg_substr");
+    out.data_bytes = total;
+    share_validity(a.col, &out);
+    v.col = out;
+    return v;
   }
   throw StageError(BG_ERR_INVALID, "plan: unknown expression node");
 }
@@ -1311,46 +1368,98 @@ static int32_t cmp_code(const std::string& s) {
   throw StageError(BG_ERR_INVALID, "filter: unknown cmp '" + s + "'");
 }
 
+// column-to-column compare names ({"cmp": ..., "rhs": {"col": ...}}); lt,
+// eq and gt overlap the literal forms, the presence of "rhs" selects these
+static int32_t cmp_cols_code(const std::string& s) {
+  if (s == "lt") return BG_CMP_LT;
+  if (s == "le") return BG_CMP_LE;
+  if (s == "gt") return BG_CMP_GT;
+  if (s == "ge") return BG_CMP_GE;
+  if (s == "eq") return BG_CMP_EQ;
+  if (s == "ne") return BG_CMP_NE;
+  throw StageError(BG_ERR_INVALID,
+                   "filter: unknown column compare '" + s +
+                       "' (lt/le/gt/ge/eq/ne)");
+}
+
+static bool in_values_are_strings(const Value& p) {
+  auto& vals = p.get_arr("in");
+  return !vals.empty() && vals[0]->kind == Value::STR;
+}
+
+// AND-fold one predicate group into a fresh mask.  Every predicate's
+// operand is resolved ONCE to an index into `cols`: a named column is used
+// in place, an "expr" operand is evaluated to a temporary column that lives
+// until the call returns.  Evaluation order narrows the mask cheapest
+// first: literal compares and IN lists, then LIKE, then column-to-column
+// compares (whose kernel skips words that are already zero).
 static DBufPtr eval_filter_mask(const Table& t, const Value& node) {
   auto& preds = node.get_arr("predicates");
   std::vector<bg_column> cols;
   for (auto& c : t.cols) cols.push_back(to_bg(c, t.n));
+  std::vector<Col> temps;  // keep "expr" operands' buffers alive
+  struct Pred { const Value* p; int operand; };
+  auto resolve = [&](const Value& p) -> int {
+    if (!p.has("expr")) return t.idx(p.get_str("col"));
+    ExprVal v = eval_expr(t, p.at("expr"));
+    if (v.is_lit)
+      throw StageError(BG_ERR_INVALID, "filter: literal predicate operand");
+    temps.push_back(v.col);
+    cols.push_back(to_bg(temps.back(), t.n));
+    return (int)cols.size() - 1;
+  };
   std::vector<bg_pred> bp;
-  std::vector<const Value*> likes;
-  std::vector<const Value*> ins;
+  std::vector<Pred> likes, ins, rhss;
   for (auto& p : preds) {
-    if (p->has("like")) {
-      likes.push_back(p.get());
-      continue;
+    const int operand = resolve(*p);
+    if (p->has("rhs")) {
+      rhss.push_back({p.get(), operand});
+    } else if (p->has("like")) {
+      likes.push_back({p.get(), operand});
+    } else if (p->has("in")) {
+      ins.push_back({p.get(), operand});
+    } else {
+      bg_pred q{};
+      q.column = operand;
+      q.op = cmp_code(p->get_str("cmp"));
+      if (p->has("lo")) parse_i128(p->at("lo"), &q.lo_lo, &q.lo_hi);
+      if (p->has("hi")) parse_i128(p->at("hi"), &q.hi_lo, &q.hi_hi);
+      bp.push_back(q);
     }
-    if (p->has("in")) {
-      ins.push_back(p.get());
-      continue;
-    }
-    bg_pred q{};
-    q.column = t.idx(p->get_str("col"));
-    q.op = cmp_code(p->get_str("cmp"));
-    if (p->has("lo")) parse_i128(p->at("lo"), &q.lo_lo, &q.lo_hi);
-    if (p->has("hi")) parse_i128(p->at("hi"), &q.hi_lo, &q.hi_hi);
-    bp.push_back(q);
   }
   DBufPtr mask = alloc_bitmap(t.n, bp.empty() ? 0xFF : -1);
   if (!bp.empty())
     chk(bg_eval_predicates(cols.data(), (int32_t)cols.size(), bp.data(),
                            (int32_t)bp.size(), t.n, mask->u8()),
         "bg_eval_predicates");
-  for (auto* ip : ins) {
-    std::vector<int64_t> vals;
-    for (auto& v : ip->get_arr("in")) {
+  for (auto& ip : ins) {
+    const bg_column& c = cols[(size_t)ip.operand];
+    auto& vals = ip.p->get_arr("in");
+    if (in_values_are_strings(*ip.p)) {
+      std::vector<const char*> strs;
+      std::vector<int32_t> lens;
+      for (auto& v : vals) {
+        if (v->kind != Value::STR)
+          throw StageError(BG_ERR_INVALID, "filter: mixed 'in' value kinds");
+        strs.push_back(v->s.c_str());
+        lens.push_back((int32_t)v->s.size());
+      }
+      chk(bg_eval_in_utf8(&c, strs.data(), lens.data(), (int32_t)strs.size(),
+                          t.n, mask->u8()),
+          "bg_eval_in_utf8");
+      continue;
+    }
+    std::vector<int64_t> ivals;
+    for (auto& v : vals) {
       int64_t lo, hi;
       parse_i128(*v, &lo, &hi);
-      vals.push_back(lo);
+      ivals.push_back(lo);
     }
-    bg_column c = to_bg(t.col(ip->get_str("col")), t.n);
-    chk(bg_eval_in(&c, vals.data(), (int32_t)vals.size(), t.n, mask->u8()),
+    chk(bg_eval_in(&c, ivals.data(), (int32_t)ivals.size(), t.n, mask->u8()),
         "bg_eval_in");
   }
-  for (auto* lp : likes) {
+  for (auto& lk : likes) {
+    const Value* lp = lk.p;
     // split the LIKE pattern into in-order literal fragments + anchors
     const std::string& pat = lp->get_str("like");
     const bool anchor_prefix = !pat.empty() && pat.front() != '%';
@@ -1377,12 +1486,20 @@ static DBufPtr eval_filter_mask(const Table& t, const Value& node) {
       terms.push_back(f.c_str());
       lens.push_back((int32_t)f.size());
     }
-    bg_column c = to_bg(t.col(lp->get_str("col")), t.n);
+    const bg_column& c = cols[(size_t)lk.operand];
     chk(bg_eval_like(&c, terms.data(), lens.data(), (int32_t)terms.size(),
                      anchor_prefix ? 1 : 0, anchor_suffix ? 1 : 0,
                      lp->get_bool_or("negate", false) ? 1 : 0, t.n,
                      mask->u8()),
         "bg_eval_like");
+  }
+  for (auto& rp : rhss) {
+    const bg_column& a = cols[(size_t)rp.operand];
+    const bg_column& b =
+        cols[(size_t)t.idx(rp.p->at("rhs").get_str("col"))];
+    chk(bg_eval_compare_cols(&a, &b, cmp_cols_code(rp.p->get_str("cmp")), t.n,
+                             mask->u8()),
+        "bg_eval_compare_cols");
   }
   return mask;
 }
@@ -2814,6 +2931,72 @@ struct VSchema {
 
 static DtSpec validate_expr(const VSchema& s, const Value& e);
 
+// how an error message names an operand: the column, or the expression
+// node with the operand inside it, e.g. substr(c_phone)
+static std::string expr_label(const Value& e) {
+  if (e.has("col")) return e.get_str("col");
+  for (const char* k : {"date_part", "substr"})
+    if (e.has(k))
+      return std::string(k) + "(" + expr_label(e.at(k).at("arg")) + ")";
+  return e.kind == Value::OBJ && !e.obj.empty() ? e.obj[0].first : "?";
+}
+
+// The one predicate validator: filter groups and case.when both use it.
+// Operand is {"col"} or {"expr"}; the form is column-to-column ("rhs"),
+// LIKE, IN (string values iff the operand is utf8) or a literal cmp.
+static void validate_predicate(const VSchema& s, const Value& p) {
+  DtSpec opd;
+  std::string name;
+  if (p.has("expr")) {
+    opd = validate_expr(s, p.at("expr"));
+    name = expr_label(p.at("expr"));
+  } else {
+    name = p.get_str("col");
+    opd = s.dts[(size_t)s.idx(name)];
+  }
+  if (p.has("rhs")) {
+    for (const char* k : {"lo", "hi", "like", "in"})
+      if (p.has(k))
+        throw StageError(BG_ERR_INVALID,
+                         "filter: 'rhs' compare on '" + name +
+                             "' cannot also carry '" + k + "'");
+    cmp_cols_code(p.get_str("cmp"));
+    const std::string& rname = p.at("rhs").get_str("col");
+    const DtSpec r = s.dts[(size_t)s.idx(rname)];
+    const std::string pair = "'" + name + "' (" + dtype_name(opd.dt) +
+                             ") vs rhs '" + rname + "' (" +
+                             dtype_name(r.dt) + ")";
+    if (opd.dt != r.dt)
+      throw StageError(BG_ERR_INVALID,
+                       "filter: rhs compare dtype mismatch: " + pair);
+    if (opd.dt == BG_DT_FLOAT64 || opd.dt == BG_DT_UTF8)
+      throw StageError(BG_ERR_UNSUPPORTED,
+                       "filter: rhs compare of float64/utf8 columns: " + pair);
+    if (opd.dt == BG_DT_DECIMAL128 && opd.scale != r.scale)
+      throw StageError(BG_ERR_INVALID,
+                       "filter: rhs compare scale mismatch: " + pair +
+                           ", scales " + std::to_string(opd.scale) + " and " +
+                           std::to_string(r.scale));
+    return;
+  }
+  if (p.has("like")) return;
+  if (p.has("in")) {
+    const bool strs = in_values_are_strings(p);
+    if (strs != (opd.dt == BG_DT_UTF8))
+      throw StageError(BG_ERR_INVALID,
+                       std::string("filter: 'in' with ") +
+                           (strs ? "string" : "integer") + " values on '" +
+                           name + "' (" + dtype_name(opd.dt) + ")");
+    return;
+  }
+  cmp_code(p.get_str("cmp"));
+}
+
+static void validate_predicates(const VSchema& s,
+                                const std::vector<ValuePtr>& preds) {
+  for (auto& p : preds) validate_predicate(s, *p);
+}
+
 static VSchema validate_plan(const Value& node) {
   const std::string op = node.get_str("op");
   if (op == "scan") {
@@ -2839,17 +3022,10 @@ static VSchema validate_plan(const Value& node) {
   }
   if (op == "filter") {
     VSchema s = validate_plan(node.at("input"));
-    auto check_group = [&](const std::vector<ValuePtr>& preds) {
-      for (auto& p : preds) {
-        s.idx(p->get_str("col"));
-        if (p->has("like") || p->has("in")) continue;
-        cmp_code(p->get_str("cmp"));
-      }
-    };
     if (node.has("any"))
-      for (auto& grp : node.get_arr("any")) check_group(grp->arr);
+      for (auto& grp : node.get_arr("any")) validate_predicates(s, grp->arr);
     else
-      check_group(node.get_arr("predicates"));
+      validate_predicates(s, node.get_arr("predicates"));
     return s;
   }
   if (op == "project") {
@@ -2918,10 +3094,7 @@ static DtSpec validate_expr(const VSchema& s, const Value& e) {
   if (e.has("lit")) return {BG_DT_DECIMAL128, 38, 0};
   if (e.has("case")) {
     const Value& c = e.at("case");
-    for (auto& p : c.get_arr("when")) {
-      s.idx(p->get_str("col"));
-      if (!p->has("like")) cmp_code(p->get_str("cmp"));
-    }
+    validate_predicates(s, c.get_arr("when"));
     DtSpec a = validate_expr(s, c.at("then"));
     DtSpec b = validate_expr(s, c.at("else"));
     return a.dt == BG_DT_DECIMAL128 || b.dt != BG_DT_DECIMAL128 ? a : b;
@@ -2936,6 +3109,37 @@ static DtSpec validate_expr(const VSchema& s, const Value& e) {
                                                                     : b.scale);
       return {BG_DT_DECIMAL128, 38, scale};
     }
+  }
+  if (e.has("date_part")) {
+    const Value& d = e.at("date_part");
+    date_part_code(d.get_str("part"));
+    const DtSpec a = validate_expr(s, d.at("arg"));
+    if (a.dt != BG_DT_DATE32)
+      throw StageError(BG_ERR_INVALID,
+                       "date_part: argument '" + expr_label(d.at("arg")) +
+                           "' is " + dtype_name(a.dt) + ", date32 required");
+    return {BG_DT_INT32, 0, 0};
+  }
+  if (e.has("substr")) {
+    const Value& d = e.at("substr");
+    const DtSpec a = validate_expr(s, d.at("arg"));
+    const std::string arg = expr_label(d.at("arg"));
+    if (a.dt != BG_DT_UTF8)
+      throw StageError(BG_ERR_INVALID, "substr: argument '" + arg + "' is " +
+                                           dtype_name(a.dt) +
+                                           ", utf8 required");
+    for (const char* k : {"start", "count"})
+      if (d.has(k) && d.at(k).kind != Value::INT)
+        throw StageError(BG_ERR_UNSUPPORTED,
+                         std::string("substr: '") + k + "' of '" + arg +
+                             "' must be an integer literal");
+    d.get_int("start");
+    if (d.has("count") && d.get_int("count") < 0)
+      throw StageError(BG_ERR_INVALID,
+                       "substr: negative substring length not allowed "
+                       "(count " + std::to_string(d.get_int("count")) +
+                           " on '" + arg + "')");
+    return {BG_DT_UTF8, 0, 0};
   }
   throw StageError(BG_ERR_INVALID, "plan: unknown expression node");
 }

@@ -33,6 +33,20 @@ BG_PRED_LT = 2
 BG_PRED_EQ = 3
 BG_PRED_GT = 4
 
+BG_DATE_PART_YEAR = 0
+BG_DATE_PART_QUARTER = 1
+BG_DATE_PART_MONTH = 2
+BG_DATE_PART_DAY = 3
+BG_DATE_PART_DOY = 4
+BG_DATE_PART_DOW = 5
+
+BG_CMP_LT = 0
+BG_CMP_LE = 1
+BG_CMP_GT = 2
+BG_CMP_GE = 3
+BG_CMP_EQ = 4
+BG_CMP_NE = 5
+
 BG_AGG_OP_SUM_DEC128 = 0
 BG_AGG_OP_SUM_I64 = 1
 BG_AGG_OP_MIN_I64 = 2
@@ -168,7 +182,9 @@ _SIGNATURES = {
     "bg_sub_i32": "i plip", "bg_gather_bits": "i pplp",
     "bg_eval_like": "i pSpiiiilp", "bg_select": "i pppllp",
     "bg_fill_const": "i pllll", "bg_eval_in": "i ppilp",
-    "bg_bitmap_or": "i pplp", "bg_hash_columns": "i pilp",
+    "bg_bitmap_or": "i pplp", "bg_date_part": "i pilp",
+    "bg_substr": "i plillpplp", "bg_eval_compare_cols": "i ppilp",
+    "bg_eval_in_utf8": "i pSpilp", "bg_hash_columns": "i pilp",
     "bg_partition_ids": "i plup", "bg_partition_indices": "i plupp",
     "bg_partition_indices_ex": "i pluppp", "bg_scatter_rows": "i plplp",
     "bg_hash_repartition": "i pipiluppP", "bg_hashjoin_build": "i plP",
@@ -446,6 +462,51 @@ class GpuStageContext:
                                        max_bytes, ctypes.byref(total)),
                "bg_gather_varlen")
         return out_offs, out_data, total.value
+
+    # ---- scalar expressions ----
+    def date_part(self, col: BgColumn, part: int, n: int) -> DeviceBuffer:
+        """date_part(part, Date32 column) -> device i32[n] (BG_DATE_PART_*);
+        the result shares the input's validity."""
+        out = self.alloc(max(4 * n, 4))
+        _check(self.L.bg_date_part(ctypes.byref(col), part, n, out.ptr),
+               "bg_date_part")
+        return out
+
+    def substr(self, col: BgColumn, start: int, count: int = None,
+               n: int = None):
+        """substr(Utf8 column, start[, count]) in code points -> (offsets
+        buf i32[n+1], data buf, total bytes); sized exactly first."""
+        n = col.len if n is None else n
+        has_count, cnt = (0, 0) if count is None else (1, count)
+        out_offs = self.alloc(max(4 * (n + 1), 8))
+        total = ctypes.c_int64()
+        _check(self.L.bg_substr(ctypes.byref(col), start, has_count, cnt, n,
+                                out_offs.ptr, None, 0, ctypes.byref(total)),
+               "bg_substr(size)")
+        out_data = self.alloc(max(total.value, 1))
+        _check(self.L.bg_substr(ctypes.byref(col), start, has_count, cnt, n,
+                                out_offs.ptr, out_data.ptr, total.value,
+                                ctypes.byref(total)), "bg_substr")
+        return out_offs, out_data, total.value
+
+    def compare_cols(self, a: BgColumn, b: BgColumn, cmp: int, n: int,
+                     mask: DeviceBuffer) -> DeviceBuffer:
+        """AND `a <cmp> b` (BG_CMP_*) into the existing device mask."""
+        _check(self.L.bg_eval_compare_cols(ctypes.byref(a), ctypes.byref(b),
+                                           cmp, n, mask.ptr),
+               "bg_eval_compare_cols")
+        return mask
+
+    def in_utf8(self, col: BgColumn, values, n: int,
+                mask: DeviceBuffer) -> DeviceBuffer:
+        """AND `col IN (values)` (list[bytes], exact byte equality) into the
+        existing device mask."""
+        varr = (ctypes.c_char_p * len(values))(*values)
+        larr = (ctypes.c_int32 * len(values))(*[len(v) for v in values])
+        _check(self.L.bg_eval_in_utf8(ctypes.byref(col), varr, larr,
+                                      len(values), n, mask.ptr),
+               "bg_eval_in_utf8")
+        return mask
 
     # ---- hash repartition ----
     def hash_columns(self, key_cols, n: int) -> DeviceBuffer:

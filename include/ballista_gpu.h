@@ -185,6 +185,65 @@ int bg_eval_in(const bg_column* col, const int64_t* values, int32_t nvalues,
 int bg_bitmap_or(const uint8_t* d_a, const uint8_t* d_b, int64_t nbits,
                  uint8_t* d_out);
 
+/* ---- scalar expressions beyond Decimal128 arithmetic and column-vs-
+ * literal predicates.  Null semantics as everywhere: a predicate over a
+ * NULL input is false; a projection leaves validity to the caller (share
+ * the input's bitmap); value bytes under a NULL are unspecified. ---- */
+
+/* date_part(part, Date32) -> Int32, as DataFusion 55's date_part on Date32
+ * (approved/q7.txt:67, q8.txt:93, q9.txt:65: ProjectionExec
+ * date_part(YEAR, o_orderdate) as o_year, then GROUP BY it).  Proleptic
+ * Gregorian with floor division: exact for every int32 day number, before
+ * 1970 and before year 0 included.  d_out: n x 4 B.  Other parts return
+ * BG_ERR_UNSUPPORTED, a non-Date32 column BG_ERR_INVALID. */
+#define BG_DATE_PART_YEAR 0
+#define BG_DATE_PART_QUARTER 1
+#define BG_DATE_PART_MONTH 2
+#define BG_DATE_PART_DAY 3
+#define BG_DATE_PART_DOY 4      /* 1..366 */
+#define BG_DATE_PART_DOW 5      /* Sunday = 0, as DataFusion */
+int bg_date_part(const bg_column* col /* DATE32 */, int32_t part, int64_t n,
+                 int32_t* d_out);
+
+/* substr(str, start[, count]) over a Utf8 column, as DataFusion's substr
+ * (approved/q22.txt:3,13,16: substr(c_phone, 1, 2) as filter operand and
+ * as the projected GROUP BY key cntrycode).  1-based, counted in UTF-8
+ * CODE POINTS: with s = start-1 and e = has_count ? s+count : len the
+ * result is code points [clamp(s,0,len), clamp(e,0,len)) — start <= 0
+ * eats into the count, start > len gives ''.  count < 0 is refused
+ * (BG_ERR_INVALID, "negative substring length not allowed").  NULL rows
+ * produce zero bytes.  Outputs as bg_gather_varlen: Arrow i32 offsets
+ * (n+1) + packed bytes; d_out_data == NULL is a sizing call returning
+ * *out_total_bytes; a total above 2 GiB is BG_ERR_INVALID.  Cost per row
+ * is O(start+count) bytes walked, not O(len). */
+int bg_substr(const bg_column* col /* UTF8 */, int64_t start, int32_t has_count,
+              int64_t count, int64_t n, int32_t* d_out_offsets /* n+1 */,
+              void* d_out_data, int64_t out_data_cap, int64_t* out_total_bytes);
+
+/* a <cmp> b between two COLUMNS, ANDed into an existing bitmask
+ * (approved/q4.txt:8, q12.txt:3, q21.txt:7,53: FilterExec
+ * l_receiptdate > l_commitdate, l_shipdate < l_commitdate on the lineitem
+ * scan).  Same dtype on both sides, one of INT32/DATE32/INT64/DICT8/
+ * DECIMAL128 (signed i128; equal scale required, the plan serialiser
+ * presents coerced types); FLOAT64/UTF8 return BG_ERR_UNSUPPORTED.  Words
+ * of d_mask that are already zero cost no column traffic, so run the
+ * literal predicates first.  Bits at or beyond n come out 0. */
+#define BG_CMP_LT 0
+#define BG_CMP_LE 1
+#define BG_CMP_GT 2
+#define BG_CMP_GE 3
+#define BG_CMP_EQ 4
+#define BG_CMP_NE 5
+int bg_eval_compare_cols(const bg_column* a, const bg_column* b, int32_t cmp,
+                         int64_t n, uint8_t* d_mask);
+
+/* x IN {v0..v15} over a Utf8 column by exact byte equality, ANDed into an
+ * existing bitmask (approved/q22.txt:3,16: substr(c_phone, 1, 2) IN
+ * ('13', '31', ...)).  1..16 literals of 1..64 bytes each. */
+int bg_eval_in_utf8(const bg_column* col, const char* const* values,
+                    const int32_t* value_lens, int32_t nvalues, int64_t n,
+                    uint8_t* d_mask);
+
 /* ---- hash repartition (SortShuffleWriterExec device half) ---- */
 
 /* create_hashes restatement over the key columns (bg_ahash.h; parity
