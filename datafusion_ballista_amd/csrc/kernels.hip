@@ -6819,6 +6819,192 @@ __global__ void k_join_fill_mark2(KeyArgs bkeys, KeyArgs pkeys,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Join residual filters (HashJoinExec with filter: Some(JoinFilter);
+// approved/q21.txt:60-61, q7.txt, q19.txt).  The filter decides which
+// key-equal candidates count as matches, so it runs inside the chain walk,
+// in front of the join type's bookkeeping.  It is an OR of groups, each an
+// AND of: one bit of a build-side mask, one bit of a probe-side mask (the
+// caller evaluated the single-side predicates into them) and up to four
+// build-column <cmp> probe-column compares.  The program travels as a
+// kernel argument like KeyArgs; every loop bound over it is wave-uniform.
+// Kernels of their own, so the unfiltered ones above stay as they were.
+// ---------------------------------------------------------------------------
+struct JoinFilterArgs {
+  int ngroups;
+  struct Group {
+    const uint8_t* build_mask;  // Arrow LSB bits over build rows, or null
+    const uint8_t* probe_mask;  // over this launch's probe rows, or null
+    int ncross;
+    struct Cross {
+      const void* b;
+      const uint8_t* bvalid;
+      const void* p;
+      const uint8_t* pvalid;
+      int dtype;
+      int cmp;
+    } x[BG_JOIN_FILTER_MAX_CROSS];
+  } g[BG_JOIN_FILTER_MAX_GROUPS];
+};
+
+template <typename T>
+__device__ __forceinline__ bool jf_compare(T x, T y, int cmp) {
+  switch (cmp) {
+    case BG_CMP_LT: return x < y;
+    case BG_CMP_LE: return x <= y;
+    case BG_CMP_GT: return x > y;
+    case BG_CMP_GE: return x >= y;
+    case BG_CMP_EQ: return x == y;
+    default: return x != y;  // BG_CMP_NE (host checked the range)
+  }
+}
+
+// one cross term: validity first (NULL on either side fails the term),
+// Decimal128 as signed i128 like cmp_load<i128>
+__device__ __forceinline__ bool jf_cross_passes(
+    const JoinFilterArgs::Group::Cross& x, int64_t b, int64_t p) {
+  if (!bit_valid(x.bvalid, b) || !bit_valid(x.pvalid, p)) return false;
+  switch (x.dtype) {
+    case BG_DT_INT64:
+      return jf_compare(reinterpret_cast<const int64_t*>(x.b)[b],
+                        reinterpret_cast<const int64_t*>(x.p)[p], x.cmp);
+    case BG_DT_INT32:
+    case BG_DT_DATE32:
+      return jf_compare(reinterpret_cast<const int32_t*>(x.b)[b],
+                        reinterpret_cast<const int32_t*>(x.p)[p], x.cmp);
+    case BG_DT_DICT8:
+      return jf_compare(reinterpret_cast<const uint8_t*>(x.b)[b],
+                        reinterpret_cast<const uint8_t*>(x.p)[p], x.cmp);
+    case BG_DT_DECIMAL128:
+      return jf_compare(load_dec128(x.b, b), load_dec128(x.p, p), x.cmp);
+    default:
+      return false;  // the host refuses every other dtype
+  }
+}
+
+// the groups whose probe-side mask keeps probe row p; 0 = no candidate of
+// this row can pass, whatever its key
+__device__ __forceinline__ uint32_t jf_live_groups(const JoinFilterArgs& f,
+                                                   int64_t p) {
+  uint32_t live = 0;
+  for (int g = 0; g < f.ngroups; ++g)
+    if (bit_valid(f.g[g].probe_mask, p)) live |= 1u << g;
+  return live;
+}
+
+// THE decision "candidate (build row b, probe row p) passes": the count,
+// fill and mark walks all call it, so they cannot disagree (count sizes the
+// slots fill writes into).  First failing term ends a group, first passing
+// group ends the test.
+__device__ __forceinline__ bool jf_candidate_passes(const JoinFilterArgs& f,
+                                                    uint32_t live, int64_t b,
+                                                    int64_t p) {
+  for (int g = 0; g < f.ngroups; ++g) {
+    if (!((live >> g) & 1)) continue;
+    if (!bit_valid(f.g[g].build_mask, b)) continue;
+    int c = 0;
+    while (c < f.g[g].ncross && jf_cross_passes(f.g[g].x[c], b, p)) ++c;
+    if (c == f.g[g].ncross) return true;
+  }
+  return false;
+}
+
+// k_join_count2 over passing candidates.  A probe row with no live group
+// skips the hash and the walk.
+__global__ void k_join_count2f(KeyArgs bkeys, KeyArgs pkeys, int64_t n_probe,
+                               const int* head, const ulong2* nodes, u64 mask,
+                               int32_t join_type, JoinFilterArgs f,
+                               uint32_t* counts) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < n_probe; i += (int64_t)gridDim.x * blockDim.x) {
+    u64 cnt = 0;
+    const uint32_t live = jf_live_groups(f, i);
+    if (live && !row_has_null_key(pkeys, i)) {
+      const u64 h = hash_keys_row(pkeys, i);
+      int64_t cur = head[h & mask];
+      while (cur >= 0) {
+        const ulong2 node = nodes[cur];
+        if (node.x == h && keys_equal_cross(bkeys, cur, pkeys, i) &&
+            jf_candidate_passes(f, live, cur, i)) {
+          ++cnt;
+          if (join_type == BG_JOIN_SEMI || join_type == BG_JOIN_ANTI) break;
+        }
+        cur = (int64_t)node.y;
+      }
+    }
+    switch (join_type) {
+      case BG_JOIN_INNER: break;
+      case BG_JOIN_SEMI: cnt = cnt ? 1 : 0; break;
+      case BG_JOIN_ANTI: cnt = cnt ? 0 : 1; break;
+      case BG_JOIN_OUTER_PROBE: cnt = cnt ? cnt : 1; break;
+      default: break;
+    }
+    counts[i] = (uint32_t)cnt;
+  }
+}
+
+// k_join_fill2 (MARK=false: INNER/SEMI/ANTI/OUTER_PROBE) and
+// k_join_fill_mark2 (MARK=true: INNER or OUTER_PROBE pairs, each passing
+// candidate's build row marked) over passing candidates; writes exactly the
+// slots k_join_count2f counted for the same join_type and filter.
+template <bool MARK>
+__global__ void k_join_fill2f(KeyArgs bkeys, KeyArgs pkeys, int64_t n_probe,
+                              const int* head, const ulong2* nodes, u64 mask,
+                              int32_t join_type, JoinFilterArgs f,
+                              const i64* offsets, uint32_t* out_probe,
+                              uint32_t* out_build, uint32_t* visited) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < n_probe; i += (int64_t)gridDim.x * blockDim.x) {
+    i64 w = offsets[i];
+    bool matched = false;
+    const uint32_t live = jf_live_groups(f, i);
+    if (live && !row_has_null_key(pkeys, i)) {
+      const u64 h = hash_keys_row(pkeys, i);
+      int64_t cur = head[h & mask];
+      while (cur >= 0) {
+        const ulong2 node = nodes[cur];
+        if (node.x == h && keys_equal_cross(bkeys, cur, pkeys, i) &&
+            jf_candidate_passes(f, live, cur, i)) {
+          matched = true;
+          if (join_type != BG_JOIN_ANTI) {
+            out_probe[w] = (uint32_t)i;
+            out_build[w] = (uint32_t)cur;
+            ++w;
+          }
+          if (MARK) mark_visited(visited, cur);
+          if (join_type == BG_JOIN_SEMI || join_type == BG_JOIN_ANTI) break;
+        }
+        cur = (int64_t)node.y;
+      }
+    }
+    if (!matched &&
+        (join_type == BG_JOIN_ANTI || join_type == BG_JOIN_OUTER_PROBE)) {
+      out_probe[w] = (uint32_t)i;
+      out_build[w] = BG_JOIN_NULL_IDX;
+    }
+  }
+}
+
+// k_join_mark2 over passing candidates: walks to the chain's end
+__global__ void k_join_mark2f(KeyArgs bkeys, KeyArgs pkeys, int64_t n_probe,
+                              const int* head, const ulong2* nodes, u64 mask,
+                              JoinFilterArgs f, uint32_t* visited) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < n_probe; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t live = jf_live_groups(f, i);
+    if (!live || row_has_null_key(pkeys, i)) continue;
+    const u64 h = hash_keys_row(pkeys, i);
+    int64_t cur = head[h & mask];
+    while (cur >= 0) {
+      const ulong2 node = nodes[cur];
+      if (node.x == h && keys_equal_cross(bkeys, cur, pkeys, i) &&
+          jf_candidate_passes(f, live, cur, i))
+        mark_visited(visited, cur);
+      cur = (int64_t)node.y;
+    }
+  }
+}
+
 // ~visited (or all ones where nothing was ever marked) as a mask for the
 // stable compaction, which trims the bits at or beyond n itself
 __global__ void k_bitmap_not_u64(const u64* in, int64_t nwords, u64* out) {
@@ -6864,7 +7050,11 @@ struct BgJoinTable2 {
   // one visited bit per build row, ((n_build+63)/64)*8 + 8 bytes; allocated
   // and zeroed by the first marking call, accumulated until free2
   uint32_t* visited = nullptr;
+  // the filter of the last bg_hashjoin_probe_count2_filtered, which stores
+  // probe_jt with JOIN_JT_FILTERED set: a fill must repeat both
+  JoinFilterArgs probe_filter = {};
 };
+#define JOIN_JT_FILTERED 0x100
 
 static inline uint64_t join_visited_bytes(int64_t n_build) {
   return (uint64_t)((n_build + 63) / 64) * 8 + 8;
@@ -7058,6 +7248,180 @@ extern "C" int bg_hashjoin_build_rows2(void* handle, int32_t matched,
   HIP_TRY(hipGetLastError());
   return mask_to_indices(reinterpret_cast<const uint8_t*>(inv.get()),
                          t->n_build, d_out_build, out_count);
+}
+
+// flat ABI terms -> the kernels' grouped program, every limit checked
+static int join_filter_args(const bg_join_filter_term* terms, int32_t nterms,
+                            int64_t n_build, int64_t n_probe,
+                            JoinFilterArgs* f) {
+  if (nterms <= 0 || !terms)
+    return set_err(BG_ERR_INVALID,
+                   "join filter: no terms (a join without a filter goes "
+                   "through the unfiltered entries)");
+  memset(f, 0, sizeof(*f));
+  bool seen[BG_JOIN_FILTER_MAX_GROUPS] = {};
+  for (int32_t i = 0; i < nterms; ++i) {
+    const bg_join_filter_term& t = terms[i];
+    if (t.group < 0 || t.group >= BG_JOIN_FILTER_MAX_GROUPS)
+      return set_err(BG_ERR_INVALID, "join filter: group id outside [0,4)");
+    JoinFilterArgs::Group& g = f->g[t.group];
+    seen[t.group] = true;
+    if (t.group + 1 > f->ngroups) f->ngroups = t.group + 1;
+    switch (t.kind) {
+      case BG_JF_BUILD_MASK:
+        if (!t.d_build || g.build_mask)
+          return set_err(BG_ERR_INVALID,
+                         "join filter: null or second build mask in a group");
+        g.build_mask = reinterpret_cast<const uint8_t*>(t.d_build);
+        break;
+      case BG_JF_PROBE_MASK:
+        if (!t.d_probe || g.probe_mask)
+          return set_err(BG_ERR_INVALID,
+                         "join filter: null or second probe mask in a group");
+        g.probe_mask = reinterpret_cast<const uint8_t*>(t.d_probe);
+        break;
+      case BG_JF_CROSS: {
+        if (t.cmp < BG_CMP_LT || t.cmp > BG_CMP_NE)
+          return set_err(BG_ERR_INVALID, "join filter: unknown cmp");
+        if (t.dtype == BG_DT_FLOAT64 || t.dtype == BG_DT_UTF8)
+          return set_err(BG_ERR_UNSUPPORTED,
+                         "join filter: cross compare of Float64/Utf8 columns");
+        if (t.dtype != BG_DT_INT32 && t.dtype != BG_DT_INT64 &&
+            t.dtype != BG_DT_DATE32 && t.dtype != BG_DT_DECIMAL128 &&
+            t.dtype != BG_DT_DICT8)
+          return set_err(BG_ERR_INVALID, "join filter: unknown dtype");
+        // an empty side may come without buffers; nothing indexes it
+        if ((!t.d_build && n_build > 0) || (!t.d_probe && n_probe > 0))
+          return set_err(BG_ERR_INVALID, "join filter: null cross column");
+        if (g.ncross == BG_JOIN_FILTER_MAX_CROSS)
+          return set_err(BG_ERR_INVALID,
+                         "join filter: more than 4 cross terms in a group");
+        JoinFilterArgs::Group::Cross& x = g.x[g.ncross++];
+        x.b = t.d_build;
+        x.bvalid = t.d_build_validity;
+        x.p = t.d_probe;
+        x.pvalid = t.d_probe_validity;
+        x.dtype = t.dtype;
+        x.cmp = t.cmp;
+        break;
+      }
+      default:
+        return set_err(BG_ERR_INVALID, "join filter: unknown term kind");
+    }
+  }
+  for (int g = 0; g < f->ngroups; ++g)
+    if (!seen[g])
+      return set_err(BG_ERR_INVALID,
+                     "join filter: group ids must be dense from 0 (an empty "
+                     "group would pass everything)");
+  return BG_OK;
+}
+
+extern "C" int bg_hashjoin_probe_count2_filtered(
+    void* handle, const bg_column* keys, int32_t nkeys, int64_t n,
+    int32_t join_type, const bg_join_filter_term* terms, int32_t nterms,
+    int64_t* out_matches) {
+  REQUIRE_INIT();
+  BgJoinTable2* t = (BgJoinTable2*)handle;
+  if (!t || !out_matches)
+    return set_err(BG_ERR_INVALID, "null join handle / out_matches");
+  KeyArgs pk;
+  int rc = join_probe_keys(t, keys, nkeys, &pk);
+  if (rc != BG_OK) return rc;
+  if ((rc = join_refuse_pairless(join_type)) != BG_OK) return rc;
+  if (join_type < BG_JOIN_INNER || join_type > BG_JOIN_OUTER_FULL)
+    return set_err(BG_ERR_INVALID, "unknown join_type");
+  JoinFilterArgs f;
+  if ((rc = join_filter_args(terms, nterms, t->n_build, n, &f)) != BG_OK) return rc;
+  // the marking types count pairs exactly as the type they extend
+  const int32_t count_jt = join_type == BG_JOIN_OUTER_BUILD
+                               ? BG_JOIN_INNER
+                               : join_type == BG_JOIN_OUTER_FULL
+                                     ? BG_JOIN_OUTER_PROBE
+                                     : join_type;
+  if (t->probe_offsets) {
+    (void)pool_release(t->probe_offsets);
+    t->probe_offsets = nullptr;
+  }
+  DevBuf<uint32_t> d_counts;
+  DevBuf<i64> d_offs;
+  DevBuf<i64> d_total;
+  HIP_TRY(d_counts.alloc(n));
+  HIP_TRY(d_offs.alloc(n));
+  HIP_TRY(d_total.alloc(1));
+  hipLaunchKernelGGL(k_join_count2f, dim3(grid_for(n)), dim3(BG_BLOCK), 0, 0,
+                     t->bkeys, pk, n, t->head, t->nodes, t->mask, count_jt, f,
+                     d_counts.get());
+  HIP_TRY(hipGetLastError());
+  rc = scan_exclusive_u32(d_counts, n, d_offs, d_total);
+  if (rc != BG_OK) return rc;
+  i64 total = 0;
+  HIP_TRY(hipMemcpy(&total, d_total, sizeof(i64), hipMemcpyDeviceToHost));
+  t->probe_offsets = d_offs.detach();  // the handle owns it until free2
+  t->probe_n = n;
+  t->probe_jt = join_type | JOIN_JT_FILTERED;
+  t->probe_filter = f;
+  *out_matches = total;
+  return BG_OK;
+}
+
+extern "C" int bg_hashjoin_probe_fill2_filtered(
+    void* handle, const bg_column* keys, int32_t nkeys, int64_t n,
+    int32_t join_type, const bg_join_filter_term* terms, int32_t nterms,
+    uint32_t* d_out_probe, uint32_t* d_out_build) {
+  REQUIRE_INIT();
+  BgJoinTable2* t = (BgJoinTable2*)handle;
+  if (!t) return set_err(BG_ERR_INVALID, "null join handle");
+  KeyArgs pk;
+  int rc = join_probe_keys(t, keys, nkeys, &pk);
+  if (rc != BG_OK) return rc;
+  if ((rc = join_refuse_pairless(join_type)) != BG_OK) return rc;
+  JoinFilterArgs f;
+  if ((rc = join_filter_args(terms, nterms, t->n_build, n, &f)) != BG_OK) return rc;
+  // the offsets are only good for the filter they were counted under
+  if (!t->probe_offsets || t->probe_n != n ||
+      t->probe_jt != (join_type | JOIN_JT_FILTERED) ||
+      memcmp(&f, &t->probe_filter, sizeof(f)) != 0)
+    return set_err(BG_ERR_INVALID,
+                   "call bg_hashjoin_probe_count2_filtered first (same "
+                   "join_type, same terms)");
+  const int blocks = grid_for(n);
+  if (join_type == BG_JOIN_OUTER_BUILD || join_type == BG_JOIN_OUTER_FULL) {
+    if ((rc = join_ensure_visited(t)) != BG_OK) return rc;
+    hipLaunchKernelGGL(k_join_fill2f<true>, dim3(blocks), dim3(BG_BLOCK), 0,
+                       0, t->bkeys, pk, n, t->head, t->nodes, t->mask,
+                       join_type == BG_JOIN_OUTER_FULL ? BG_JOIN_OUTER_PROBE
+                                                       : BG_JOIN_INNER,
+                       f, t->probe_offsets, d_out_probe, d_out_build,
+                       t->visited);
+  } else {
+    hipLaunchKernelGGL(k_join_fill2f<false>, dim3(blocks), dim3(BG_BLOCK), 0,
+                       0, t->bkeys, pk, n, t->head, t->nodes, t->mask,
+                       join_type, f, t->probe_offsets, d_out_probe,
+                       d_out_build, (uint32_t*)nullptr);
+  }
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+extern "C" int bg_hashjoin_probe_mark2_filtered(
+    void* handle, const bg_column* keys, int32_t nkeys, int64_t n,
+    const bg_join_filter_term* terms, int32_t nterms) {
+  REQUIRE_INIT();
+  BgJoinTable2* t = (BgJoinTable2*)handle;
+  if (!t) return set_err(BG_ERR_INVALID, "null join handle");
+  KeyArgs pk;
+  int rc = join_probe_keys(t, keys, nkeys, &pk);
+  if (rc != BG_OK) return rc;
+  JoinFilterArgs f;
+  if ((rc = join_filter_args(terms, nterms, t->n_build, n, &f)) != BG_OK) return rc;
+  if ((rc = join_ensure_visited(t)) != BG_OK) return rc;
+  if (n <= 0) return BG_OK;
+  hipLaunchKernelGGL(k_join_mark2f, dim3(grid_for(n)), dim3(BG_BLOCK), 0, 0,
+                     t->bkeys, pk, n, t->head, t->nodes, t->mask, f,
+                     t->visited);
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
 }
 
 // sentinel handling for probe-outer joins: split an index vector carrying

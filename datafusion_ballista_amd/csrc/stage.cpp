@@ -1613,17 +1613,21 @@ static JoinOut join_output(const JoinKind& k, const Value& o) {
   return {build, col, o.get_str_or("as", col)};
 }
 
-// The hash table of one join: the single-INT64-key inner join has a
-// specialised table, every other shape goes through the general one.
+// The hash table of one join: the single-INT64-key inner join without a
+// residual filter has a specialised table, every other shape goes through
+// the general one.  The probe calls take the chunk's filter terms; none
+// means no filter.
+using JoinTerms = std::vector<bg_join_filter_term>;
 struct JoinHandle {
   void* h = nullptr;
   const bool fast;
   const int32_t type;
   JoinHandle(const JoinHandle&) = delete;
   JoinHandle& operator=(const JoinHandle&) = delete;
-  JoinHandle(const std::vector<bg_column>& bk, int64_t n, int32_t join_type)
+  JoinHandle(const std::vector<bg_column>& bk, int64_t n, int32_t join_type,
+             bool filtered)
       : fast(bk.size() == 1 && bk[0].dtype == BG_DT_INT64 &&
-             join_type == BG_JOIN_INNER),
+             join_type == BG_JOIN_INNER && !filtered),
         type(join_type) {
     if (fast) chk(bg_hashjoin_build(&bk[0], n, &h), "bg_hashjoin_build");
     else
@@ -1633,32 +1637,49 @@ struct JoinHandle {
   ~JoinHandle() {
     if (h) (void)(fast ? bg_hashjoin_free(h) : bg_hashjoin_free2(h));
   }
-  int64_t count(const std::vector<bg_column>& pk, int64_t len) {
+  int64_t count(const std::vector<bg_column>& pk, int64_t len,
+                const JoinTerms& ft) {
     int64_t matches = 0;
     if (fast)
       chk(bg_hashjoin_probe_count(h, &pk[0], len, &matches),
           "bg_hashjoin_probe_count");
-    else
+    else if (ft.empty())
       chk(bg_hashjoin_probe_count2(h, pk.data(), (int32_t)pk.size(), len,
                                    type, &matches),
           "bg_hashjoin_probe_count2");
+    else
+      chk(bg_hashjoin_probe_count2_filtered(h, pk.data(), (int32_t)pk.size(),
+                                            len, type, ft.data(),
+                                            (int32_t)ft.size(), &matches),
+          "bg_hashjoin_probe_count2_filtered");
     return matches;
   }
-  void fill(const std::vector<bg_column>& pk, int64_t len, uint32_t* pidx,
-            uint32_t* bidx) {
+  void fill(const std::vector<bg_column>& pk, int64_t len,
+            const JoinTerms& ft, uint32_t* pidx, uint32_t* bidx) {
     if (fast)
       chk(bg_hashjoin_probe_fill(h, &pk[0], len, pidx, bidx),
           "bg_hashjoin_probe_fill");
-    else
+    else if (ft.empty())
       chk(bg_hashjoin_probe_fill2(h, pk.data(), (int32_t)pk.size(), len, type,
                                   pidx, bidx),
           "bg_hashjoin_probe_fill2");
+    else
+      chk(bg_hashjoin_probe_fill2_filtered(h, pk.data(), (int32_t)pk.size(),
+                                           len, type, ft.data(),
+                                           (int32_t)ft.size(), pidx, bidx),
+          "bg_hashjoin_probe_fill2_filtered");
   }
   // the build-rows calls exist for the general table only; the types that
   // use them never take the fast path
-  void mark(const std::vector<bg_column>& pk, int64_t len) {
-    chk(bg_hashjoin_probe_mark2(h, pk.data(), (int32_t)pk.size(), len),
-        "bg_hashjoin_probe_mark2");
+  void mark(const std::vector<bg_column>& pk, int64_t len,
+            const JoinTerms& ft) {
+    if (ft.empty())
+      chk(bg_hashjoin_probe_mark2(h, pk.data(), (int32_t)pk.size(), len),
+          "bg_hashjoin_probe_mark2");
+    else
+      chk(bg_hashjoin_probe_mark2_filtered(h, pk.data(), (int32_t)pk.size(),
+                                           len, ft.data(), (int32_t)ft.size()),
+          "bg_hashjoin_probe_mark2_filtered");
   }
   // build rows some probe row matched (matched=1) or none did (0), in
   // ascending build order
@@ -1689,6 +1710,83 @@ struct JoinSides {
                    int64_t rows) const {
     return gather_col(build.col(col), build.n, (const uint32_t*)idx->p, rows);
   }
+
+  // The residual filter ("filter": {"any": [group...]}), evaluated as far
+  // as one side alone allows: each group's "build" and "probe" predicates
+  // become one mask over that side's whole table, its "cross" terms stay
+  // column pairs for the probe kernels.  No groups = no filter.
+  struct FilterGroup {
+    DBufPtr build_mask, probe_mask;
+    struct Cross { int bcol, pcol; int32_t cmp; };
+    std::vector<Cross> cross;
+  };
+  std::vector<FilterGroup> filter;
+
+  void eval_filter(const Value& node) {
+    if (!node.has("filter")) return;
+    // AND-fold a group's predicate list over one side, like a filter node
+    auto side_mask = [](const Table& t, const Value& grp, const char* key) {
+      for (auto& kv : grp.obj) {
+        if (kv.first != key || kv.second->arr.empty()) continue;
+        bgjson::Value fake;
+        fake.kind = Value::OBJ;
+        fake.obj.emplace_back("predicates", kv.second);
+        return eval_filter_mask(t, fake);
+      }
+      return DBufPtr();
+    };
+    for (auto& grp : node.at("filter").get_arr("any")) {
+      FilterGroup g;
+      g.build_mask = side_mask(build, *grp, "build");
+      g.probe_mask = side_mask(probe, *grp, "probe");
+      if (grp->has("cross"))
+        for (auto& x : grp->get_arr("cross"))
+          g.cross.push_back({build.idx(x->get_str("build")),
+                             probe.idx(x->get_str("probe")),
+                             cmp_cols_code(x->get_str("cmp"))});
+      filter.push_back(std::move(g));
+    }
+  }
+
+  // the filter's terms for the probe slice [start, start+len): start is a
+  // 64-row multiple, so the slice's probe mask starts at a byte of the
+  // whole table's and the cross columns slice like the keys
+  JoinTerms filter_terms(int64_t start, int64_t len) const {
+    JoinTerms terms;
+    for (size_t gi = 0; gi < filter.size(); ++gi) {
+      const FilterGroup& g = filter[gi];
+      bg_join_filter_term t{};
+      t.group = (int32_t)gi;
+      if (g.build_mask) {
+        t.kind = BG_JF_BUILD_MASK;
+        t.d_build = g.build_mask->p;
+        terms.push_back(t);
+      }
+      if (g.probe_mask) {
+        t = bg_join_filter_term{};
+        t.group = (int32_t)gi;
+        t.kind = BG_JF_PROBE_MASK;
+        t.d_probe = g.probe_mask->u8() + start / 8;
+        terms.push_back(t);
+      }
+      for (auto& x : g.cross) {
+        const Col& bc = build.cols[(size_t)x.bcol];
+        // the slice owns nothing: its pointers stay good while probe lives
+        const Col pc = slice_col(probe.cols[(size_t)x.pcol], start, len);
+        t = bg_join_filter_term{};
+        t.group = (int32_t)gi;
+        t.kind = BG_JF_CROSS;
+        t.dtype = bc.dtype;
+        t.cmp = x.cmp;
+        t.d_build = bc.dptr();
+        t.d_build_validity = bc.vptr();
+        t.d_probe = pc.dptr();
+        t.d_probe_validity = pc.vptr();
+        terms.push_back(t);
+      }
+    }
+    return terms;
+  }
 };
 
 // semi_build / anti_build: only the visited bitmap matters: mark per probe
@@ -1701,7 +1799,7 @@ static Table join_build_rows_only(JoinHandle& jh, const JoinSides& s,
     std::vector<bg_column> pk;
     std::vector<Col> pk_sliced;
     s.slice_probe_keys(start, len, pk_sliced, pk);
-    jh.mark(pk, len);
+    jh.mark(pk, len, s.filter_terms(start, len));
   }
   DBufPtr idx = dalloc_elems(s.build.n, 4);
   Table out;
@@ -1722,10 +1820,11 @@ static int64_t join_probe_chunk(JoinHandle& jh, const JoinKind& k,
   std::vector<bg_column> pk;
   std::vector<Col> pk_sliced;
   s.slice_probe_keys(start, len, pk_sliced, pk);
-  const int64_t matches = jh.count(pk, len);
+  const JoinTerms ft = s.filter_terms(start, len);
+  const int64_t matches = jh.count(pk, len, ft);
   DBufPtr pidx = dalloc_elems(matches, 4);
   DBufPtr bidx = dalloc_elems(matches, 4);
-  jh.fill(pk, len, (uint32_t*)pidx->p, (uint32_t*)bidx->p);
+  jh.fill(pk, len, ft, (uint32_t*)pidx->p, (uint32_t*)bidx->p);
 
   DBufPtr bidx_clamped, outer_valid;
   if (k.probe_null_idx) {
@@ -1797,7 +1896,8 @@ static Table exec_join(const Value& node, Metrics& m) {
       throw StageError(BG_ERR_INVALID, "hash_join: key dtype mismatch");
   }
   for (auto& o : node.get_arr("output")) s.outs.push_back(join_output(k, *o));
-  JoinHandle jh(bk, s.build.n, k.type);
+  s.eval_filter(node);
+  JoinHandle jh(bk, s.build.n, k.type, !s.filter.empty());
 
   // Memory-pressure bound (the spill analogue of sort_shuffle/writer.rs:
   // 650-686 for join temporaries): probe in slices of probe_chunk_rows
@@ -2997,6 +3097,118 @@ static void validate_predicates(const VSchema& s,
   for (auto& p : preds) validate_predicate(s, *p);
 }
 
+// every {"col": name} under a predicate (operand, rhs, expression leaves)
+static void pred_columns(const Value& v, std::vector<std::string>& out) {
+  for (auto& kv : v.obj) {
+    if (kv.first == "col" && kv.second->kind == Value::STR)
+      out.push_back(kv.second->s);
+    else
+      pred_columns(*kv.second, out);
+  }
+  for (auto& e : v.arr) pred_columns(*e, out);
+}
+
+static bool schema_has(const VSchema& s, const std::string& n) {
+  return std::find(s.names.begin(), s.names.end(), n) != s.names.end();
+}
+
+// one side's predicate list of a join filter group: the ordinary pred
+// grammar, over that side's columns only
+static void validate_join_filter_side(const VSchema& own, const VSchema& other,
+                                      const char* side, const char* other_side,
+                                      const Value& preds) {
+  for (auto& p : preds.arr) {
+    std::vector<std::string> names;
+    pred_columns(*p, names);
+    for (auto& n : names)
+      if (!schema_has(own, n))
+        throw StageError(
+            BG_ERR_INVALID,
+            std::string("hash_join filter: '") + side + "' predicate names '" +
+                n + "', " +
+                (schema_has(other, n)
+                     ? std::string("a column of the ") + other_side + " side"
+                     : std::string("a column of neither side")));
+    validate_predicate(own, *p);
+  }
+}
+
+// hash_join "filter": {"any": [{build?, probe?, cross?}...]}; b and p are
+// the build and probe schemas
+static void validate_join_filter(const VSchema& b, const VSchema& p,
+                                 const Value& filt) {
+  auto& groups = filt.get_arr("any");
+  if (groups.empty())
+    throw StageError(BG_ERR_INVALID,
+                     "hash_join filter: empty 'any' (omit the filter)");
+  if (groups.size() > BG_JOIN_FILTER_MAX_GROUPS)
+    throw StageError(BG_ERR_UNSUPPORTED,
+                     "hash_join filter: " + std::to_string(groups.size()) +
+                         " groups in 'any', at most 4");
+  for (size_t gi = 0; gi < groups.size(); ++gi) {
+    const Value& g = *groups[gi];
+    const std::string where = "hash_join filter: group " + std::to_string(gi);
+    size_t nterms = 0;
+    if (g.has("build")) {
+      validate_join_filter_side(b, p, "build", "probe", g.at("build"));
+      nterms += g.get_arr("build").size();
+    }
+    if (g.has("probe")) {
+      validate_join_filter_side(p, b, "probe", "build", g.at("probe"));
+      nterms += g.get_arr("probe").size();
+    }
+    if (g.has("cross")) {
+      auto& cross = g.get_arr("cross");
+      nterms += cross.size();
+      if (cross.size() > BG_JOIN_FILTER_MAX_CROSS)
+        throw StageError(BG_ERR_UNSUPPORTED,
+                         where + " has " + std::to_string(cross.size()) +
+                             " cross terms, at most 4");
+      for (auto& x : cross) {
+        const std::string& bn = x->get_str("build");
+        const std::string& pn = x->get_str("probe");
+        const std::string& cmp = x->get_str("cmp");
+        if (!schema_has(b, bn))
+          throw StageError(BG_ERR_INVALID,
+                           where + ": cross term's build column '" + bn +
+                               "' is not a column of the build side");
+        if (!schema_has(p, pn))
+          throw StageError(BG_ERR_INVALID,
+                           where + ": cross term's probe column '" + pn +
+                               "' is not a column of the probe side");
+        try {
+          cmp_cols_code(cmp);
+        } catch (const StageError&) {
+          throw StageError(BG_ERR_INVALID,
+                           where + ": unknown cross cmp '" + cmp +
+                               "' (lt/le/gt/ge/eq/ne)");
+        }
+        const DtSpec bd = b.dts[(size_t)b.idx(bn)];
+        const DtSpec pd = p.dts[(size_t)p.idx(pn)];
+        const std::string pair = "build '" + bn + "' (" + dtype_name(bd.dt) +
+                                 ") vs probe '" + pn + "' (" +
+                                 dtype_name(pd.dt) + ")";
+        if (bd.dt != pd.dt)
+          throw StageError(BG_ERR_INVALID,
+                           where + ": cross term dtype mismatch: " + pair);
+        if (bd.dt == BG_DT_FLOAT64 || bd.dt == BG_DT_UTF8)
+          throw StageError(BG_ERR_UNSUPPORTED,
+                           where + ": cross term over float64/utf8 columns: " +
+                               pair);
+        if (bd.dt == BG_DT_DECIMAL128 && bd.scale != pd.scale)
+          throw StageError(BG_ERR_INVALID,
+                           where + ": cross term scale mismatch: " + pair +
+                               ", scales " + std::to_string(bd.scale) +
+                               " and " + std::to_string(pd.scale));
+      }
+    }
+    if (nterms == 0)
+      throw StageError(BG_ERR_INVALID,
+                       where + " is empty (always true: omit the filter "
+                               "instead)");
+  }
+}
+
 static VSchema validate_plan(const Value& node) {
   const std::string op = node.get_str("op");
   if (op == "scan") {
@@ -3043,6 +3255,7 @@ static VSchema validate_plan(const Value& node) {
     for (auto& k : node.get_arr("build_keys")) b.idx(k->s);
     for (auto& k : node.get_arr("probe_keys")) p.idx(k->s);
     const JoinKind& k = join_kind(node);
+    if (node.has("filter")) validate_join_filter(b, p, node.at("filter"));
     VSchema out;
     for (auto& ov : node.get_arr("output")) {
       const JoinOut o = join_output(k, *ov);

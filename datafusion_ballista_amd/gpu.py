@@ -47,6 +47,12 @@ BG_CMP_GE = 3
 BG_CMP_EQ = 4
 BG_CMP_NE = 5
 
+BG_JOIN_FILTER_MAX_GROUPS = 4
+BG_JOIN_FILTER_MAX_CROSS = 4
+BG_JF_CROSS = 0
+BG_JF_BUILD_MASK = 1
+BG_JF_PROBE_MASK = 2
+
 BG_AGG_OP_SUM_DEC128 = 0
 BG_AGG_OP_SUM_I64 = 1
 BG_AGG_OP_MIN_I64 = 2
@@ -157,6 +163,12 @@ class BgPackJob(ctypes.Structure):
                 ("size_word", _u32), ("_pad", _u32)]
 
 
+class BgJoinFilterTerm(ctypes.Structure):
+    _fields_ = [("kind", _i32), ("group", _i32), ("dtype", _i32),
+                ("cmp", _i32), ("d_build", _p), ("d_build_validity", _p),
+                ("d_probe", _p), ("d_probe_validity", _p)]
+
+
 # ---- function signatures: "<return> <one code per parameter>" ----
 # Every data pointer is a c_void_p, which takes None, an int address, a
 # c_void_p, byref(...), a ctypes array or a POINTER instance alike.
@@ -193,6 +205,9 @@ _SIGNATURES = {
     "bg_hashjoin_probe_count2": "i ppilip",
     "bg_hashjoin_probe_fill2": "i ppilipp", "bg_hashjoin_free2": "i p",
     "bg_hashjoin_probe_mark2": "i ppil", "bg_hashjoin_build_rows2": "i pipp",
+    "bg_hashjoin_probe_count2_filtered": "i ppilipip",
+    "bg_hashjoin_probe_fill2_filtered": "i ppilipipp",
+    "bg_hashjoin_probe_mark2_filtered": "i ppilpi",
     "bg_idx_sentinel": "i plpp", "bg_bitmap_and": "i pplp",
     "bg_hashagg": "i pippipllpppp", "bg_hashagg2": "i pippipllppppp",
     "bg_project_dec128": "i ipplllp",

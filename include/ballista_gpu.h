@@ -363,6 +363,61 @@ int bg_hashjoin_probe_mark2(void* handle, const bg_column* keys, int32_t nkeys,
 int bg_hashjoin_build_rows2(void* handle, int32_t matched, int64_t* out_count,
                             uint32_t* d_out_build);
 
+/* ---- join residual filters ----
+ * DataFusion 55 HashJoinExec with `filter: Some(JoinFilter)` (wire format:
+ * JoinFilter, datafusion.proto:1402; HashJoinExecNode.filter = 8,
+ * datafusion.proto:1189; approved/q21.txt:60-61, q7.txt, q19.txt).  A
+ * CANDIDATE is a (build row, probe row) pair with equal non-NULL keys, as
+ * above; it PASSES when the filter is TRUE (NULL counts as FALSE), and
+ * every join type then reads "match" as "passing candidate": SEMI emits a
+ * probe row with >=1 passing candidate (the walk goes on past failing
+ * ones), ANTI one with none, the outer types extend rows without one, and
+ * only passing candidates set a build row's visited bit.
+ *
+ * The filter is an OR of up to BG_JOIN_FILTER_MAX_GROUPS groups, each an
+ * AND of its terms, handed over as a flat array of terms.  A group holds at
+ * most one build mask, one probe mask and BG_JOIN_FILTER_MAX_CROSS cross
+ * compares; group ids are dense from 0.  Single-side predicates are
+ * evaluated by the caller into masks (bg_eval_predicates and its kin); a
+ * cross compare follows bg_eval_compare_cols: equal dtypes among
+ * Int32/Int64/Date32/Decimal128 (signed i128; equal scales are the
+ * caller's to check)/dict8, a NULL on either side fails the term. */
+#define BG_JOIN_FILTER_MAX_GROUPS 4
+#define BG_JOIN_FILTER_MAX_CROSS 4
+#define BG_JF_CROSS 0       /* d_build[build row] <cmp> d_probe[probe row] */
+#define BG_JF_BUILD_MASK 1  /* d_build: Arrow LSB bitmap over the build rows */
+#define BG_JF_PROBE_MASK 2  /* d_probe: Arrow LSB bitmap over THIS call's probe rows */
+typedef struct {
+  int32_t kind;   /* BG_JF_* */
+  int32_t group;  /* 0 .. BG_JOIN_FILTER_MAX_GROUPS-1 */
+  int32_t dtype;  /* BG_JF_CROSS: bg_dtype of both columns */
+  int32_t cmp;    /* BG_JF_CROSS: BG_CMP_* */
+  const void* d_build;             /* cross: build column data; build mask */
+  const uint8_t* d_build_validity; /* cross: or NULL (all valid) */
+  const void* d_probe;             /* cross: probe column data; probe mask */
+  const uint8_t* d_probe_validity; /* cross: or NULL (all valid) */
+} bg_join_filter_term;
+
+/* bg_hashjoin_probe_count2 / _fill2 / _mark2 with a filter; join_type as
+ * there (count/fill refuse types 4 and 5, mark serves them).  The fill
+ * call must repeat the count call's terms.  nterms == 0 is BG_ERR_INVALID:
+ * a join without a filter goes through the unfiltered entries. */
+int bg_hashjoin_probe_count2_filtered(void* handle, const bg_column* keys,
+                                      int32_t nkeys, int64_t n,
+                                      int32_t join_type,
+                                      const bg_join_filter_term* terms,
+                                      int32_t nterms, int64_t* out_matches);
+int bg_hashjoin_probe_fill2_filtered(void* handle, const bg_column* keys,
+                                     int32_t nkeys, int64_t n,
+                                     int32_t join_type,
+                                     const bg_join_filter_term* terms,
+                                     int32_t nterms, uint32_t* d_out_probe,
+                                     uint32_t* d_out_build);
+int bg_hashjoin_probe_mark2_filtered(void* handle, const bg_column* keys,
+                                     int32_t nkeys, int64_t n,
+                                     const bg_join_filter_term* terms,
+                                     int32_t nterms);
+
 /* Split an index vector carrying BG_JOIN_NULL_IDX sentinels (probe-outer
  * build side) into a clamped gather-safe vector + the validity bitmap of
  * non-sentinel slots. */

@@ -2,11 +2,12 @@
 """Stage-interpreter fuzz: random tables (dtypes x NULLs x cardinalities)
 through random plan trees (filter -> optional hash join -> group-by
 aggregate [-> sort/limit]), every run checked against pyarrow compute.
-Covers the plan grammar end to end: expression eval, LIKE, join types,
-partial/final over a real shuffle file round trip (every 5th round).
+Covers the plan grammar end to end: expression eval, LIKE, join types with
+and without a residual filter, partial/final over a real shuffle file round trip (every 5th round).
 
 Usage: python scripts/fuzz_stage.py [rounds] [seed]"""
 import decimal
+import operator
 import os
 import sys
 import tempfile
@@ -152,9 +153,12 @@ def run_round(ctx, rng, trial, tmpdir):
     nb = int(rng.integers(10, 500))
     bkeys = rng.choice(np.arange(0, max(2, n // 50), dtype=np.int64),
                        size=nb, replace=True)
-    bt = pa.table({"bk": pa.array(np.unique(bkeys)),
-                   "bv": pa.array(np.arange(len(np.unique(bkeys)),
-                                            dtype=np.int64))})
+    ubk = np.unique(bkeys)
+    bw = rng.integers(-10**8, 10**8, size=len(ubk), dtype=np.int64)
+    bwmask = rng.random(len(ubk)) < 0.1
+    bt = pa.table({"bk": pa.array(ubk),
+                   "bv": pa.array(np.arange(len(ubk), dtype=np.int64)),
+                   "bw": pa.array(bw, mask=bwmask)})
     keep2 = stage.register_table(ctx, name + "b", bt)
     jp = {"op": "hash_join",
           "build": {"op": "scan", "schema": stage.schema_json(bt.schema),
@@ -162,13 +166,31 @@ def run_round(ctx, rng, trial, tmpdir):
           "probe": scan, "build_keys": ["bk"], "probe_keys": ["k"],
           "join_type": jt,
           "output": [{"side": "probe", "col": "k"}]}
-    res3 = stage.execute(doc({"op": "collect", "input": jp}))
-    bset = set(np.unique(bkeys).tolist())
+    # build keys are unique: a probe row has at most one candidate, and
+    # matches when that candidate passes the filter (if there is one)
+    bw_of = {int(k): None if m else int(w)
+             for k, w, m in zip(ubk, bw, bwmask)}
     kv = t["k"].to_numpy()
+    matched = np.array([int(x) in bw_of for x in kv])
+    if rng.random() < 0.5:
+        cmp = str(rng.choice(["lt", "le", "gt", "ge", "eq", "ne"]))
+        groups = [{"cross": [{"build": "bw", "cmp": cmp, "probe": "v"}]}]
+        op = getattr(operator, cmp)
+        vv = t["v"].to_pylist()
+        ok = np.array([matched[i] and vv[i] is not None and
+                       bw_of[int(kv[i])] is not None and
+                       op(bw_of[int(kv[i])], vv[i]) for i in range(n)])
+        if rng.random() < 0.5:      # OR a probe-side group
+            cut = int(rng.integers(8000, 11000))
+            groups.append({"probe": [{"col": "d", "cmp": "lt", "hi": cut}]})
+            ok |= matched & (d_np < cut)
+        jp["filter"] = {"any": groups}
+        matched = ok
+    res3 = stage.execute(doc({"op": "collect", "input": jp}))
     if jt == "inner" or jt == "semi":
-        want_n = sum(1 for x in kv if int(x) in bset)
+        want_n = int(matched.sum())
     elif jt == "anti":
-        want_n = sum(1 for x in kv if int(x) not in bset)
+        want_n = n - int(matched.sum())
     else:
         want_n = n
     assert len(res3["rows"]) == want_n, (trial, jt, len(res3["rows"]),
