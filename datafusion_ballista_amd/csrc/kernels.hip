@@ -1821,16 +1821,77 @@ extern "C" int bg_hashjoin_free(void* handle) {
 // bit-inverted, positives sign-flipped — IEEE total order incl. infs),
 // MIN stores the complement so atomicMax + zero identity works for both.
 
+// MIN/MAX over Int32/Date32 (the I32 ops): the sign-extended value in the
+// I64 encoding above — a 32-bit value fits it, so one atomicMax is enough.
+// MIN/MAX over Decimal128/Utf8 (the ROW ops): no 128-bit atomic min/max
+// exists and a string has no fixed width, so word 0 holds the WINNING
+// INPUT ROW + 1 (0 = none yet, the claim word's encoding) and the value is
+// gathered from that row afterwards.  A row replaces the holder with one
+// CAS only where its value is STRICTLY better, so the word only improves,
+// ties never swap and the loop ends; the input is read-only during the
+// launch, so relaxed atomics suffice.  Which of several tied rows wins is
+// not deterministic, the value gathered from it is.  Order: signed i128
+// for Decimal128, bytewise unsigned lexicographic for Utf8 (Arrow's string
+// order, as the reference's DataFusion Min/Max accumulators compare).
+
+struct AggCol {
+  const void* data;
+  const uint8_t* valid;    // Arrow LSB validity or NULL (all valid)
+  const int32_t* offsets;  // Utf8 only (the ROW ops compare through it)
+  int op;
+  int dtype;  // BG_DT_*: picks the ROW ops' comparison
+};
+
 struct AggArgs {
   int naggs;
   int vmode;  // 1: record carries a per-agg non-null count word (SQL needs
               // it to report SUM/MIN/MAX of an all-NULL group as NULL)
-  struct {
-    const void* data;
-    const uint8_t* valid;  // Arrow LSB validity or NULL (all valid)
-    int op;
-  } a[BG_MAX_AGGS];
+  AggCol a[BG_MAX_AGGS];
 };
+
+// three-way compare of rows r1, r2 of a Decimal128 or Utf8 column
+__device__ __forceinline__ int agg_rows_cmp(const AggCol& c, int64_t r1,
+                                            int64_t r2) {
+  if (c.dtype == BG_DT_DECIMAL128) {
+    const ulong2 a = reinterpret_cast<const ulong2*>(c.data)[r1];
+    const ulong2 b = reinterpret_cast<const ulong2*>(c.data)[r2];
+    // i128: high limb signed, low limb unsigned
+    if (a.y != b.y) return (i64)a.y < (i64)b.y ? -1 : 1;
+    if (a.x != b.x) return a.x < b.x ? -1 : 1;
+    return 0;
+  }
+  const int32_t l1 = c.offsets[r1], n1 = c.offsets[r1 + 1] - l1;
+  const int32_t l2 = c.offsets[r2], n2 = c.offsets[r2 + 1] - l2;
+  const uint8_t* d = reinterpret_cast<const uint8_t*>(c.data);
+  const int32_t m = n1 < n2 ? n1 : n2;
+  for (int32_t j = 0; j < m; ++j) {
+    const uint8_t x = d[l1 + j], y = d[l2 + j];
+    if (x != y) return x < y ? -1 : 1;
+  }
+  // a proper prefix is smaller
+  return n1 == n2 ? 0 : (n1 < n2 ? -1 : 1);
+}
+
+// MIN_ROW/MAX_ROW update of one accumulator word with candidate cand =
+// row + 1.  SCOPE: agent for the global table, workgroup for an LDS table.
+template <int SCOPE>
+__device__ __forceinline__ void agg_row_update(u64* word, u64 cand,
+                                               const AggCol& c) {
+  const bool is_max = c.op == BG_AGG_OP_MAX_ROW;
+  u64 cur = __hip_atomic_load(word, __ATOMIC_RELAXED, SCOPE);
+  while (true) {
+    if (cur != 0) {
+      if (cur == cand) return;
+      const int cmp = agg_rows_cmp(c, (int64_t)cand - 1, (int64_t)cur - 1);
+      if (is_max ? cmp <= 0 : cmp >= 0) return;  // not strictly better
+    }
+    // on failure cur becomes the word's present value: compare again
+    if (__hip_atomic_compare_exchange_strong(word, &cur, cand,
+                                             __ATOMIC_RELAXED,
+                                             __ATOMIC_RELAXED, SCOPE))
+      return;
+  }
+}
 
 __device__ __forceinline__ bool keys_equal_rows(const KeyArgs& keys,
                                                 int64_t r1, int64_t r2) {
@@ -2016,6 +2077,23 @@ __global__ void k_hashagg(KeyArgs keys, AggArgs aggs, const u64* mask_words,
           atomicMax(base, ~v);
           break;
         }
+        case BG_AGG_OP_MAX_I32: {
+          const u64 v = (u64)(i64) reinterpret_cast<const int32_t*>(
+                            aggs.a[a].data)[i] ^ 0x8000000000000000ull;
+          atomicMax(base, v);
+          break;
+        }
+        case BG_AGG_OP_MIN_I32: {
+          const u64 v = ~((u64)(i64) reinterpret_cast<const int32_t*>(
+                              aggs.a[a].data)[i] ^ 0x8000000000000000ull);
+          atomicMax(base, v);
+          break;
+        }
+        case BG_AGG_OP_MIN_ROW:
+        case BG_AGG_OP_MAX_ROW:
+          agg_row_update<__HIP_MEMORY_SCOPE_AGENT>(base, (u64)i + 1,
+                                                   aggs.a[a]);
+          break;
         default:
           break;
       }
@@ -2127,6 +2205,25 @@ __global__ void k_hashagg_lds(KeyArgs keys, AggArgs aggs,
           atomicMax((unsigned long long*)base, ~v);
           break;
         }
+        case BG_AGG_OP_MAX_I32: {
+          const u64 v = (u64)(i64) reinterpret_cast<const int32_t*>(
+                            aggs.a[a].data)[i] ^ 0x8000000000000000ull;
+          atomicMax((unsigned long long*)base, v);
+          break;
+        }
+        case BG_AGG_OP_MIN_I32: {
+          const u64 v = ~((u64)(i64) reinterpret_cast<const int32_t*>(
+                              aggs.a[a].data)[i] ^ 0x8000000000000000ull);
+          atomicMax((unsigned long long*)base, v);
+          break;
+        }
+        case BG_AGG_OP_MIN_ROW:
+        case BG_AGG_OP_MAX_ROW:
+          // row numbers are global, so the block's winner stays
+          // meaningful in the flush below
+          agg_row_update<__HIP_MEMORY_SCOPE_WORKGROUP>(base, (u64)i + 1,
+                                                       aggs.a[a]);
+          break;
         default:
           break;
       }
@@ -2177,7 +2274,15 @@ __global__ void k_hashagg_lds(KeyArgs keys, AggArgs aggs,
         case BG_AGG_OP_MIN_I64:
         case BG_AGG_OP_MAX_F64:
         case BG_AGG_OP_MIN_F64:
+        case BG_AGG_OP_MAX_I32:
+        case BG_AGG_OP_MIN_I32:
           atomicMax(g, l[0]);
+          break;
+        case BG_AGG_OP_MIN_ROW:
+        case BG_AGG_OP_MAX_ROW:
+          // the block's winner is the candidate (0: no non-NULL row here)
+          if (l[0])
+            agg_row_update<__HIP_MEMORY_SCOPE_AGENT>(g, l[0], aggs.a[a]);
           break;
         case BG_AGG_OP_SUM_F64: {
           double v;
@@ -2243,6 +2348,22 @@ static int hashagg_impl(const bg_column* key_cols, int32_t nkeys,
     return set_err(BG_ERR_INVALID, "nkeys out of range [1,4]");
   if (naggs < 0 || naggs > BG_MAX_AGGS)
     return set_err(BG_ERR_INVALID, "naggs out of range [0,8]");
+  // the ops that read their column by dtype (before any device allocation)
+  for (int i = 0; i < naggs; ++i) {
+    const int32_t op = agg_ops[i], dt = agg_cols[i].dtype;
+    if ((op == BG_AGG_OP_MIN_ROW || op == BG_AGG_OP_MAX_ROW) &&
+        dt != BG_DT_DECIMAL128 && dt != BG_DT_UTF8)
+      return set_err(BG_ERR_UNSUPPORTED,
+                     "bg_hashagg: MIN_ROW/MAX_ROW take Decimal128 or Utf8");
+    if ((op == BG_AGG_OP_MIN_ROW || op == BG_AGG_OP_MAX_ROW) &&
+        dt == BG_DT_UTF8 && !agg_cols[i].d_offsets)
+      return set_err(BG_ERR_INVALID,
+                     "bg_hashagg: Utf8 aggregate column without offsets");
+    if ((op == BG_AGG_OP_MIN_I32 || op == BG_AGG_OP_MAX_I32) &&
+        dt != BG_DT_INT32 && dt != BG_DT_DATE32)
+      return set_err(BG_ERR_UNSUPPORTED,
+                     "bg_hashagg: MIN_I32/MAX_I32 take Int32 or Date32");
+  }
   KeyArgs keys{};
   keys.nkeys = nkeys;
   for (int i = 0; i < nkeys; ++i) {
@@ -2257,7 +2378,9 @@ static int hashagg_impl(const bg_column* key_cols, int32_t nkeys,
   for (int i = 0; i < naggs; ++i) {
     aggs.a[i].data = agg_cols[i].d_data;
     aggs.a[i].valid = agg_cols[i].d_validity;
+    aggs.a[i].offsets = agg_cols[i].d_offsets;
     aggs.a[i].op = agg_ops[i];
+    aggs.a[i].dtype = agg_cols[i].dtype;
   }
   u64 cap = 8;
   while (cap < (u64)(max_groups * 2)) cap <<= 1;
@@ -6458,6 +6581,16 @@ __global__ void k_agg_materialize(const uint8_t* __restrict__ acc,
         reinterpret_cast<uint64_t*>(out)[g] = is_null ? 0 : bits;
         break;
       }
+      case BG_AGG_OP_MAX_I32: {  // 4-B out (Int32/Date32)
+        reinterpret_cast<int32_t*>(out)[g] =
+            is_null ? 0 : (int32_t)(int64_t)(lo ^ 0x8000000000000000ull);
+        break;
+      }
+      case BG_AGG_OP_MIN_I32: {
+        reinterpret_cast<int32_t*>(out)[g] =
+            is_null ? 0 : (int32_t)(int64_t)((~lo) ^ 0x8000000000000000ull);
+        break;
+      }
       default: break;
     }
   }
@@ -6469,6 +6602,11 @@ extern "C" int bg_agg_materialize(const void* d_acc, int64_t acc_stride,
                                   int64_t nncnt_stride,
                                   uint8_t* d_valid_out) {
   REQUIRE_INIT();
+  if (op == BG_AGG_OP_MIN_ROW || op == BG_AGG_OP_MAX_ROW)
+    // the record names a row of an input column this call never sees
+    return set_err(BG_ERR_INVALID,
+                   "bg_agg_materialize: MIN_ROW/MAX_ROW hold a row index "
+                   "(bg_agg_winner_rows + bg_gather)");
   if (ngroups <= 0) return BG_OK;
   int blocks =
       (int)bg_imin64((ngroups + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
@@ -6476,6 +6614,44 @@ extern "C" int bg_agg_materialize(const void* d_acc, int64_t acc_stride,
                      (const uint8_t*)d_acc, acc_stride, op, ngroups,
                      (uint8_t*)d_out, d_nncnt, nncnt_stride,
                      (uint32_t*)d_valid_out);
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+// MIN_ROW/MAX_ROW records -> gather indices + validity.  One thread owns
+// one whole byte of the bitmap (8 groups), so it needs no atomics and no
+// pre-initialised bitmap; bits past ngroups in the last byte are 0.
+__global__ void k_agg_winner_rows(const uint8_t* __restrict__ acc,
+                                  int64_t acc_stride, int64_t ngroups,
+                                  uint32_t* __restrict__ rows_out,
+                                  uint8_t* __restrict__ valid_out) {
+  const int64_t nbytes = (ngroups + 7) / 8;
+  for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < nbytes;
+       b += (int64_t)gridDim.x * blockDim.x) {
+    uint8_t bits = 0;
+    for (int j = 0; j < 8; ++j) {
+      const int64_t g = b * 8 + j;
+      if (g >= ngroups) break;
+      const uint64_t w =
+          *reinterpret_cast<const uint64_t*>(acc + g * acc_stride);
+      rows_out[g] = w ? (uint32_t)(w - 1) : 0u;
+      if (w) bits |= (uint8_t)(1u << j);
+    }
+    valid_out[b] = bits;
+  }
+}
+
+extern "C" int bg_agg_winner_rows(const void* d_acc, int64_t acc_stride,
+                                  int64_t ngroups, uint32_t* d_rows_out,
+                                  uint8_t* d_valid_out) {
+  REQUIRE_INIT();
+  if (ngroups <= 0) return BG_OK;
+  const int64_t nbytes = (ngroups + 7) / 8;
+  int blocks =
+      (int)bg_imin64((nbytes + BG_BLOCK - 1) / BG_BLOCK, BG_MAX_BLOCKS);
+  hipLaunchKernelGGL(k_agg_winner_rows, dim3(blocks), dim3(BG_BLOCK), 0, 0,
+                     (const uint8_t*)d_acc, acc_stride, ngroups, d_rows_out,
+                     d_valid_out);
   HIP_TRY(hipGetLastError());
   return BG_OK;
 }

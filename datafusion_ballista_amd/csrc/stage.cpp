@@ -2078,13 +2078,23 @@ struct AggSlots {
   }
 };
 
+// The kernel op of an aggregate over an input dtype: the one answer that
+// bg_stage_validate and execution both read.
 static int32_t agg_op_for(const std::string& fn, int32_t dt) {
   if (fn == "min" || fn == "max") {
-    if (dt == BG_DT_FLOAT64)
-      return fn == "min" ? BG_AGG_OP_MIN_F64 : BG_AGG_OP_MAX_F64;
-    if (dt != BG_DT_INT64)
-      throw StageError(BG_ERR_UNSUPPORTED, "min/max: int64/f64 only");
-    return fn == "min" ? BG_AGG_OP_MIN_I64 : BG_AGG_OP_MAX_I64;
+    const bool mn = fn == "min";
+    switch (dt) {
+      case BG_DT_FLOAT64: return mn ? BG_AGG_OP_MIN_F64 : BG_AGG_OP_MAX_F64;
+      case BG_DT_INT64: return mn ? BG_AGG_OP_MIN_I64 : BG_AGG_OP_MAX_I64;
+      case BG_DT_INT32:
+      case BG_DT_DATE32: return mn ? BG_AGG_OP_MIN_I32 : BG_AGG_OP_MAX_I32;
+      // no fixed-width atomic: the accumulator keeps the winning row
+      case BG_DT_DECIMAL128:
+      case BG_DT_UTF8: return mn ? BG_AGG_OP_MIN_ROW : BG_AGG_OP_MAX_ROW;
+      default:  // a dictionary code has no value order
+        throw StageError(BG_ERR_UNSUPPORTED,
+                         std::string("min/max over ") + dtype_name(dt));
+    }
   }
   switch (dt) {  // sum, avg and count(expr) all run a sum
     case BG_DT_DECIMAL128: return BG_AGG_OP_SUM_DEC128;
@@ -2212,9 +2222,24 @@ static Col nn_column(const HashAggRun& r, int slot) {
 }
 
 // the decoded value of a spec's slot; with an nn source, NULL where every
-// input of the group was NULL
+// input of the group was NULL.  `in` is the slot's input column: a ROW op
+// kept the winning row, so its value is a take of `in` by those rows, NULL
+// where the group had no winner.
 static Col value_column(const HashAggRun& r, const AggSpec& s,
-                        const DtSpec& dt, const NnSrc* nn) {
+                        const DtSpec& dt, const NnSrc* nn, const Col& in,
+                        int64_t n_in) {
+  if (s.op == BG_AGG_OP_MIN_ROW || s.op == BG_AGG_OP_MAX_ROW) {
+    DBufPtr rows = dalloc_elems(r.ng, 4);
+    DBufPtr valid = alloc_bitmap(r.ng, 0);
+    chk(bg_agg_winner_rows(r.acc_at(s.agg_slot), r.acc_stride(), r.ng,
+                           (uint32_t*)rows->p, valid->u8()),
+        "bg_agg_winner_rows");
+    Col cv = gather_col(in, n_in, (const uint32_t*)rows->p, r.ng);
+    cv.precision = dt.precision;
+    cv.scale = dt.scale;
+    cv.validity = valid;
+    return cv;
+  }
   Col cv = make_col(dt);
   cv.data = dalloc_elems(r.ng, dt_size(dt.dt));
   if (nn) cv.validity = alloc_bitmap(r.ng, 0xFF);
@@ -2240,21 +2265,24 @@ static Col avg_column(const HashAggRun& r, const AggSpec& s, const DtSpec& dt,
 
 // Append every aggregate's output columns; names and dtypes come from
 // agg_output_fields.
-static void materialize_aggs(const std::vector<AggSpec>& specs,
+static void materialize_aggs(const AggSlots& slots, int64_t n_in,
                              const std::string& mode, const HashAggRun& r,
                              Table& out) {
   const bool is_final = mode == "final", is_partial = mode == "partial";
-  for (auto& s : specs) {
+  for (auto& s : slots.specs) {
     const auto fields = agg_output_fields(s.fn, mode, s.as, s.in);
     const DtSpec& dt = fields[0].dt;
     std::vector<Col> cols;
+    // the slot's input column (COUNT(*) has none and never reads it)
+    static const Col no_input;
+    const Col& vin = s.agg_slot < 0 ? no_input : slots.in[(size_t)s.agg_slot];
     if (s.agg_slot < 0) {
       // COUNT(*) = the group counts: dense i64[ng] already, never NULL
       cols.push_back(make_col(dt));
       cols[0].data = r.counts;
     } else if (s.fn == "count") {
       // final: the merged count is the SUM_I64 acc itself
-      cols.push_back(is_final ? value_column(r, s, dt, nullptr)
+      cols.push_back(is_final ? value_column(r, s, dt, nullptr, vin, n_in)
                               : nn_column(r, s.agg_slot));
     } else if (s.fn == "avg" && !is_partial) {
       cols.push_back(avg_column(r, s, dt, nn_source(r, s, is_final)));
@@ -2263,7 +2291,7 @@ static void materialize_aggs(const std::vector<AggSpec>& specs,
       // "$n" companion says when it is empty)
       const NnSrc nn = nn_source(r, s, is_final);
       cols.push_back(
-          value_column(r, s, dt, s.fn == "avg" ? nullptr : &nn));
+          value_column(r, s, dt, s.fn == "avg" ? nullptr : &nn, vin, n_in));
       if (is_partial) cols.push_back(nn_column(r, s.agg_slot));
     }
     for (size_t i = 0; i < cols.size(); ++i) {
@@ -2312,7 +2340,7 @@ static Table exec_aggregate(const Value& node, Metrics& m) {
     out.cols.push_back(
         gather_col(keys[i], in.n, (const uint32_t*)r.first->p, r.ng));
   }
-  materialize_aggs(slots.specs, mode, r, out);
+  materialize_aggs(slots, in.n, mode, r, out);
   m.output_rows = r.ng;
   return out;
 }
@@ -3286,6 +3314,11 @@ static VSchema validate_plan(const Value& node) {
       } else if (fn != "count" || a->has("expr")) {
         src = validate_expr(in, a->at("expr"));
       }
+      // the executor's verdict on fn over this dtype (a final count sums
+      // its Int64 partial counts, whatever it counted)
+      const bool count_star = fn == "count" && !a->has("expr");
+      if (!count_star && !(mode == "final" && fn == "count"))
+        (void)agg_op_for(fn, src.dt);
       for (auto& f : agg_output_fields(fn, mode, as, src)) {
         out.names.push_back(f.name);
         out.dts.push_back(f.dt);
@@ -3415,6 +3448,12 @@ extern "C" int bg_stage_validate(const char* plan_json, char** out_json) {
       w.str(s.names[i]);
       w.raw(",\"dtype\":");
       w.str(dtype_name(s.dts[i].dt));
+      if (s.dts[i].dt == BG_DT_DECIMAL128) {  // as the collect root spells it
+        w.raw(",\"precision\":");
+        w.num(s.dts[i].precision);
+        w.raw(",\"scale\":");
+        w.num(s.dts[i].scale);
+      }
       w.raw("}");
     }
     w.raw("]}");

@@ -60,6 +60,10 @@ BG_AGG_OP_MAX_I64 = 3
 BG_AGG_OP_SUM_F64 = 4
 BG_AGG_OP_MIN_F64 = 5
 BG_AGG_OP_MAX_F64 = 6
+BG_AGG_OP_MIN_I32 = 7  # Int32/Date32, encoded as MIN_I64
+BG_AGG_OP_MAX_I32 = 8
+BG_AGG_OP_MIN_ROW = 9  # Decimal128/Utf8: acc word 0 = winning row + 1
+BG_AGG_OP_MAX_ROW = 10
 
 BG_PROJ_MUL = 0
 BG_PROJ_ADD = 1
@@ -223,6 +227,7 @@ _SIGNATURES = {
     "bg_lz4_compress_flat": "i plp", "bg_lz4_decompress": "i plp",
     "bg_pack_blocks": "i pl", "bg_hash_repartition_fused": "i pipilupppP",
     "bg_bitcopy": "i plpl", "bg_agg_materialize": "i plilpplp",
+    "bg_agg_winner_rows": "i pllpp",
     "bg_copy_i64_strided": "i pllp", "bg_avg_finalize": "i pliplilpp",
     "bg_execute_stage": "i sS", "bg_stage_free": "v s",
     "bg_stage_validate": "i sS", "bg_stage_register_table": "i spSil",
@@ -278,21 +283,25 @@ def _split_i128(v: int):
 
 
 def decode_agg_value(op, raw16: bytes):
-    """Accumulator bytes -> python int/float per aggregate op."""
+    """Accumulator bytes -> python int/float per aggregate op.  A ROW op
+    decodes to the winning input row, or None where the group had no
+    non-NULL input (word 0 == 0)."""
     if op in (BG_AGG_OP_SUM_DEC128, BG_AGG_OP_SUM_I64):
         return int.from_bytes(raw16, "little", signed=True)
     if op == BG_AGG_OP_SUM_F64:
         return _struct.unpack("<d", raw16[:8])[0]
     enc = int.from_bytes(raw16[:8], "little")
+    if op in (BG_AGG_OP_MIN_ROW, BG_AGG_OP_MAX_ROW):
+        return enc - 1 if enc else None
     if op in (BG_AGG_OP_MIN_F64, BG_AGG_OP_MAX_F64):
         if op == BG_AGG_OP_MIN_F64:
             enc = ~enc & 0xFFFFFFFFFFFFFFFF
         bits = (~enc & 0xFFFFFFFFFFFFFFFF) if not (enc >> 63) \
             else enc ^ (1 << 63)
         return _struct.unpack("<d", _struct.pack("<Q", bits))[0]
-    if op == BG_AGG_OP_MAX_I64:
+    if op in (BG_AGG_OP_MAX_I64, BG_AGG_OP_MAX_I32):
         v = enc ^ (1 << 63)
-    else:  # MIN_I64
+    else:  # MIN_I64, MIN_I32
         v = (~enc & 0xFFFFFFFFFFFFFFFF) ^ (1 << 63)
     return v - (1 << 64) if v >= 1 << 63 else v
 
@@ -660,6 +669,21 @@ class GpuStageContext:
                 if naggs else np.zeros((g, 0), dtype=np.int64)
             return ret + (nn,)
         return ret
+
+    def agg_winner_rows(self, acc: DeviceBuffer, acc_stride: int,
+                        ngroups: int, byte_off: int = 0):
+        """MIN_ROW/MAX_ROW records (device, acc_stride bytes apart, the
+        first at byte_off) -> (rows u32[ngroups], valid bool[ngroups]) as
+        numpy arrays: the winning input row per group (0 where none) and
+        whether the group had a non-NULL input."""
+        rows = self.alloc(max(4 * ngroups, 4))
+        valid = self.alloc(max((ngroups + 7) // 8, 1))
+        _check(self.L.bg_agg_winner_rows(acc.at(byte_off), acc_stride,
+                                         ngroups, rows.ptr, valid.ptr),
+               "bg_agg_winner_rows")
+        bits = valid.download(np.uint8, (ngroups + 7) // 8)
+        return (rows.download(np.uint32, ngroups),
+                np.unpackbits(bits, bitorder="little")[:ngroups].astype(bool))
 
     def project_dec128(self, op, a: BgColumn, b: BgColumn, lit, n):
         out = self.alloc(max(16 * n, 16))

@@ -443,6 +443,20 @@ int bg_bitmap_and(const uint8_t* d_a, const uint8_t* d_b, int64_t nbits,
 #define BG_AGG_OP_SUM_F64 4
 #define BG_AGG_OP_MIN_F64 5 /* acc = totally-ordered u64 (IEEE sign flip) */
 #define BG_AGG_OP_MAX_F64 6
+#define BG_AGG_OP_MIN_I32 7 /* Int32/Date32; acc as MIN_I64 of the sign-extended value */
+#define BG_AGG_OP_MAX_I32 8
+#define BG_AGG_OP_MIN_ROW 9 /* Decimal128/Utf8 by agg_cols[i].dtype; acc word 0 = winning row+1, 0 = none */
+#define BG_AGG_OP_MAX_ROW 10
+/* MIN/MAX over a Decimal128 or Utf8 column (the ROW ops) keep the winning
+ * INPUT ROW, not the value: no 128-bit atomic min/max exists and a string
+ * has no fixed width.  Order: signed i128; bytewise unsigned lexicographic
+ * with a proper prefix smaller ("" is a value, not NULL) — Arrow's orders,
+ * the ones the reference's DataFusion Min/Max accumulators compare by.
+ * Which of several tied rows wins is not deterministic; the value gathered
+ * from it is.  Turn the records into a column with bg_agg_winner_rows +
+ * bg_gather / bg_gather_varlen.  A ROW op over any other dtype, or an I32
+ * op over anything but Int32/Date32, returns BG_ERR_UNSUPPORTED before any
+ * device allocation. */
 int bg_hashagg(const bg_column* key_cols, int32_t nkeys,
                const bg_column* agg_cols, const int32_t* agg_ops,
                int32_t naggs, const uint8_t* d_mask, int64_t n,
@@ -745,12 +759,26 @@ int bg_bitcopy(const uint8_t* d_src_bits, int64_t nbits, uint8_t* d_dst_bits,
 
 /* Materialize bg_hashagg accumulator records into an Arrow column:
  * acc_stride in bytes between consecutive groups' records for this
- * aggregate; op = BG_AGG_OP_*; d_out element size 16 (SUM_DEC128) or 8.
- * With d_nncnt (stride bytes), groups whose non-null input count is 0 get
- * their bit cleared in d_valid_out (SQL: SUM/MIN/MAX of all-NULL = NULL). */
+ * aggregate; op = BG_AGG_OP_*; d_out element size 16 (SUM_DEC128), 4 (the
+ * I32 ops) or 8.  With d_nncnt (stride bytes), groups whose non-null input
+ * count is 0 get their bit cleared in d_valid_out (SQL: SUM/MIN/MAX of
+ * all-NULL = NULL).  BG_ERR_INVALID for the ROW ops: their record names a
+ * row of an input column this call never sees (bg_agg_winner_rows). */
 int bg_agg_materialize(const void* d_acc, int64_t acc_stride, int32_t op,
                        int64_t ngroups, void* d_out, const int64_t* d_nncnt,
                        int64_t nncnt_stride, uint8_t* d_valid_out);
+
+/* MIN_ROW/MAX_ROW records -> what a take needs: d_rows_out[g] = the
+ * group's winning input row (0 where it had no non-NULL input, so the
+ * index stays gather-safe) and bit g of d_valid_out (ceil(ngroups/8)
+ * bytes, written whole) set exactly where word 0 of the record is
+ * non-zero.  The value column is bg_gather (16-B elements) or
+ * bg_gather_varlen of the aggregate's input by d_rows_out with this
+ * validity — the Option-valued state of the reference's Min/Max
+ * accumulators (datafusion/functions-aggregate min_max.rs), NULL for a
+ * group whose inputs were all NULL. */
+int bg_agg_winner_rows(const void* d_acc, int64_t acc_stride, int64_t ngroups,
+                       uint32_t* d_rows_out, uint8_t* d_valid_out);
 
 /* Strided i64 copy (COUNT materialisation from interleaved agg records). */
 int bg_copy_i64_strided(const void* d_src, int64_t stride, int64_t n,

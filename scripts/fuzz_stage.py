@@ -32,6 +32,14 @@ def rand_table(rng, n, with_utf8=True):
     cols["d"] = pa.array(rng.integers(8000, 11000, size=n,
                                       dtype=np.int32), type=pa.date32())
     cols["x"] = pa.array(rng.standard_normal(n))
+    # Decimal(38,2) over both limbs and both signs (min/max compare i128)
+    pmask = rng.random(n) < rng.choice([0.0, 0.25])
+    wide = [int(a) * int(b) for a, b in zip(
+        rng.integers(-2**62, 2**62, size=n), rng.integers(0, 2**62, size=n))]
+    cols["p"] = pa.array(
+        [None if m else decimal.Decimal(
+            (1 if w < 0 else 0, tuple(int(c) for c in str(abs(w))), -2))
+         for w, m in zip(wide, pmask)], type=pa.decimal128(38, 2))
     if with_utf8:
         words = ["PROMO A", "alpha green", "BRASS x", "", "special req",
                  "zed"]
@@ -111,6 +119,42 @@ def run_round(ctx, rng, trial, tmpdir):
             if wx is not None:
                 assert abs(r[3] - wx) < 1e-12
             assert r[4] == want["k_count"][i].as_py()
+    else:
+        assert res["rows"] == []
+
+    # min/max over a decimal, a string and a date column (the row-index
+    # accumulators and the 32-bit ops), exact against pyarrow
+    mm_cols = ["p", "s", "d"]
+    mm_plan = {"op": "hash_aggregate", "mode": "single", "group_by": ["k"],
+               "aggs": [{"fn": fn, "as": f"{c}_{fn}", "expr": {"col": c}}
+                        for c in mm_cols for fn in ("min", "max")],
+               "input": plan}
+    res = stage.execute(doc({"op": "collect", "input": mm_plan}))
+    if ft.num_rows:
+        want = ft.group_by("k").aggregate(
+            [(c, fn) for c in mm_cols for fn in ("min", "max")]).sort_by("k")
+
+        def cells(col):
+            if pa.types.is_decimal(col.type):  # unscaled int, exact
+                out = []
+                for dv in col.to_pylist():
+                    if dv is None:
+                        out.append(None)
+                        continue
+                    sign, digits, _ = dv.as_tuple()
+                    iv = int("".join(map(str, digits)))
+                    out.append(str(-iv if sign else iv))
+                return out
+            if pa.types.is_date32(col.type):
+                return col.cast(pa.int32()).to_pylist()
+            return col.to_pylist()
+
+        got = sorted(res["rows"], key=lambda r: r[0])
+        assert len(got) == want.num_rows, (trial, len(got), want.num_rows)
+        assert [r[0] for r in got] == want["k"].to_pylist()
+        for j, nm in enumerate(f"{c}_{fn}" for c in mm_cols
+                               for fn in ("min", "max")):
+            assert [r[1 + j] for r in got] == cells(want[nm]), (trial, nm)
     else:
         assert res["rows"] == []
 
