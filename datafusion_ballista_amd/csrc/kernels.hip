@@ -4475,6 +4475,20 @@ extern "C" int bg_snappy_decompress(const bg_snappy_page* h_pages,
   return BG_OK;
 }
 
+// ULEB128 varint shared by every Parquet page walker below: reads at most 10
+// bytes (shift <= 63) from [d, end).  A varint cut off by `end`, or one
+// still continuing after 10 bytes, is malformed: returns false.
+__device__ __forceinline__ bool bg_uvarint(const uint8_t*& d,
+                                           const uint8_t* end, u64* out_v) {
+  u64 v = 0;
+  for (int sh = 0; sh <= 63 && d < end; sh += 7) {
+    const uint8_t b = *d++;
+    v |= (u64)(b & 0x7f) << sh;
+    if (!(b & 0x80)) { *out_v = v; return true; }
+  }
+  return false;
+}
+
 // ---------------------------------------------------------------------------
 // Parquet data-page extraction (PLAIN values, no nulls):
 // optional columns prefix the page with [u32 len][RLE/bit-packed def
@@ -4507,22 +4521,20 @@ __device__ void k_page_extract_body(const uint8_t* page, int64_t page_len,
       if (!ok) atomicExch(err, 2);
       s_voff = ok ? voff : -1;
     } else if (has_def) {
-      const uint32_t dlen = (uint32_t)page[0] | ((uint32_t)page[1] << 8) |
-                            ((uint32_t)page[2] << 16) |
-                            ((uint32_t)page[3] << 24);
+      uint32_t dlen = 0;
+      if (page_len < 4) ok = 0;
+      else {
+        dlen = (uint32_t)page[0] | ((uint32_t)page[1] << 8) |
+               ((uint32_t)page[2] << 16) | ((uint32_t)page[3] << 24);
+        if ((int64_t)dlen > page_len - 4) { ok = 0; dlen = 0; }
+      }
       // walk the RLE/bit-packed hybrid (bit width 1): every level must be 1
       const uint8_t* d = page + 4;
       const uint8_t* dend = d + dlen;
       int64_t seen = 0;
       while (d < dend && seen < nvals && ok) {
         u64 header = 0;
-        int shift = 0;
-        while (d < dend) {
-          const uint8_t b = *d++;
-          header |= (u64)(b & 0x7f) << shift;
-          if (!(b & 0x80)) break;
-          shift += 7;
-        }
+        if (!bg_uvarint(d, dend, &header)) { ok = 0; break; }
         if (header & 1) {  // bit-packed group: (count/8)<<1|1, 1 byte per 8
           const int64_t groups = (int64_t)(header >> 1);
           for (int64_t g = 0; g < groups && ok; ++g) {
@@ -4538,7 +4550,7 @@ __device__ void k_page_extract_body(const uint8_t* page, int64_t page_len,
           if (d >= dend) { ok = 0; break; }
           const uint8_t val = *d++;
           if (val != 1) ok = 0;
-          seen += run;
+          seen += run < nvals - seen ? run : nvals - seen;
         }
       }
       if (seen < nvals) ok = 0;
@@ -4654,9 +4666,8 @@ __device__ void k_dict_indices_body(const uint8_t* page, int64_t page_len,
   int bw = 0;
   if (lane == 0) {
     const uint8_t* d = page;
-    const uint8_t* pend = page + page_len;
     if (has_def == 2) {
-      if (d + 4 > pend) ok = 0;
+      if (page_len < 4) ok = 0;
       else {
         const uint32_t dlen = (uint32_t)d[0] | ((uint32_t)d[1] << 8) |
                               ((uint32_t)d[2] << 16) | ((uint32_t)d[3] << 24);
@@ -4664,23 +4675,17 @@ __device__ void k_dict_indices_body(const uint8_t* page, int64_t page_len,
         if (doff > page_len) ok = 0;
       }
     } else if (has_def) {
-      if (d + 4 > pend) ok = 0;
+      if (page_len < 4) ok = 0;
       else {
         const uint32_t dlen = (uint32_t)d[0] | ((uint32_t)d[1] << 8) |
                               ((uint32_t)d[2] << 16) | ((uint32_t)d[3] << 24);
         const uint8_t* dl = d + 4;
-        const uint8_t* dlend = dl + dlen;
-        if (dlend > pend) ok = 0;
+        if ((int64_t)dlen > page_len - 4) ok = 0;
+        const uint8_t* dlend = ok ? dl + dlen : dl;
         int64_t seen = 0;
         while (ok && dl < dlend && seen < nvals) {
           u64 header = 0;
-          int shift = 0;
-          while (dl < dlend) {
-            const uint8_t b = *dl++;
-            header |= (u64)(b & 0x7f) << shift;
-            if (!(b & 0x80)) break;
-            shift += 7;
-          }
+          if (!bg_uvarint(dl, dlend, &header)) { ok = 0; break; }
           if (header & 1) {
             const int64_t groups = (int64_t)(header >> 1);
             for (int64_t g = 0; g < groups && ok; ++g) {
@@ -4694,11 +4699,11 @@ __device__ void k_dict_indices_body(const uint8_t* page, int64_t page_len,
           } else {
             const int64_t run = (int64_t)(header >> 1);
             if (dl >= dlend || *dl++ != 1) ok = 0;
-            seen += run;
+            seen += run < nvals - seen ? run : nvals - seen;
           }
         }
         if (seen < nvals) ok = 0;
-        doff = 4 + dlen;
+        doff = 4 + (int64_t)dlen;
       }
     }
     if (ok) {
@@ -4731,14 +4736,9 @@ __device__ void k_dict_indices_body(const uint8_t* page, int64_t page_len,
     int64_t nsi = si;
     u64 rle_val = 0;
     if (lane == 0) {
-      if (nsi >= page_len) hok = 0;
-      int shift = 0;
-      while (hok && nsi < page_len) {
-        const uint8_t b = page[nsi++];
-        header |= (u64)(b & 0x7f) << shift;
-        if (!(b & 0x80)) break;
-        shift += 7;
-      }
+      const uint8_t* hp = page + nsi;
+      if (!bg_uvarint(hp, page + page_len, &header)) hok = 0;
+      nsi = hp - page;
       if (hok && !(header & 1)) {
         const int nb = (bw + 7) / 8;
         if (nsi + nb > page_len) hok = 0;
@@ -4756,7 +4756,8 @@ __device__ void k_dict_indices_body(const uint8_t* page, int64_t page_len,
     rle_val = (u64)bcast64((int64_t)rle_val);
     if (header & 1) {  // bit-packed: ngroups groups of 8, bw bytes each
       const int64_t groups = (int64_t)(header >> 1);
-      if (nsi + groups * bw > page_len) {
+      // (page_len - nsi) / bw, not groups * bw: a hostile count overflows
+      if (groups > (page_len - nsi) / bw) {
         if (lane == 0) atomicExch(err, 3);
         return;
       }
@@ -4851,9 +4852,9 @@ __device__ void k_def_levels_body(const bg_def_levels_job& job, int* err) {
   if (job.page_len < 4) { atomicExch(err, 3); return; }
   const uint32_t dlen = (uint32_t)page[0] | ((uint32_t)page[1] << 8) |
                         ((uint32_t)page[2] << 16) | ((uint32_t)page[3] << 24);
+  if ((int64_t)dlen > job.page_len - 4) { atomicExch(err, 3); return; }
   const uint8_t* d = page + 4;
   const uint8_t* dend = d + dlen;
-  if (dend > page + job.page_len) { atomicExch(err, 3); return; }
   int64_t s = 0;        // slot
   uint32_t cnt = 0;     // values seen
   int64_t cur_w = -1;   // current validity word index
@@ -4876,13 +4877,7 @@ __device__ void k_def_levels_body(const bg_def_levels_job& job, int* err) {
   };
   while (d < dend && s < job.nvals) {
     u64 header = 0;
-    int shift = 0;
-    while (d < dend) {
-      const uint8_t b = *d++;
-      header |= (u64)(b & 0x7f) << shift;
-      if (!(b & 0x80)) break;
-      shift += 7;
-    }
+    if (!bg_uvarint(d, dend, &header)) { atomicExch(err, 3); return; }
     if (header & 1) {  // bit-packed groups of 8, 1 byte each (bit width 1)
       const int64_t groups = (int64_t)(header >> 1);
       for (int64_t g = 0; g < groups && s < job.nvals; ++g) {
@@ -4983,16 +4978,17 @@ struct LvlRd {
         return 0;
       }
       u64 h = 0;
-      int sh = 0;
-      while (d < end) {
-        const uint8_t b = *d++;
-        h |= (u64)(b & 0x7f) << sh;
-        if (!(b & 0x80)) break;
-        sh += 7;
+      if (!bg_uvarint(d, end, &h)) {
+        ok = false;
+        return 0;
       }
       if (h & 1) {
-        bp_left = (int64_t)(h >> 1) * 8;  // groups of 8 w-bit values
-        bp_bytes = (int64_t)(h >> 1) * w;
+        // the bytes left can feed fewer than (end - d + 1) groups, so the
+        // clamp changes nothing but keeps a hostile count from overflowing
+        const u64 avail = (u64)(end - d) + 1;
+        const int64_t groups = (int64_t)((h >> 1) < avail ? (h >> 1) : avail);
+        bp_left = groups * 8;  // groups of 8 w-bit values
+        bp_bytes = groups * w;
         bitbuf = 0;
         bits = 0;
       } else {
@@ -5152,17 +5148,7 @@ struct DbpStream {
   int bw = 0;
   int64_t mb_bytes = 0;
 
-  __device__ bool varint(u64* out_v) {
-    u64 v = 0;
-    int sh = 0;
-    while (p < pend) {
-      const uint8_t b = *p++;
-      v |= (u64)(b & 0x7f) << sh;
-      if (!(b & 0x80)) { *out_v = v; return true; }
-      sh += 7;
-    }
-    return false;
-  }
+  __device__ bool varint(u64* out_v) { return bg_uvarint(p, pend, out_v); }
   __device__ bool zigzag(i64* out_v) {
     u64 v;
     if (!varint(&v)) return false;
@@ -5178,7 +5164,13 @@ struct DbpStream {
       return false;
     if (!mb_per_block || !block_size || block_size % mb_per_block)
       return false;
+    // a page header counts values in an i32: a larger block is malformed,
+    // and the bound keeps bw * mb_vals below from overflowing
+    if (block_size > 0x7fffffffull) return false;
     mb_vals = (int64_t)(block_size / mb_per_block);
+    // the spec asks for a multiple of 32; bw * mb_vals / 8 below is a whole
+    // byte count only for a multiple of 8
+    if (mb_vals % 8) return false;
     value = first;
     mb = mb_per_block;  // force new block on first next_after_first
     t = 0;
@@ -5190,7 +5182,7 @@ struct DbpStream {
     if (t >= mb_vals) { t = 0; p += mb_bytes; ++mb; }
     if (mb >= mb_per_block) {
       if (!zigzag(&min_delta)) return false;
-      if (p + mb_per_block > pend) return false;
+      if (mb_per_block > (u64)(pend - p)) return false;
       bws = p;
       p += mb_per_block;
       mb = 0;
@@ -5200,7 +5192,7 @@ struct DbpStream {
       bw = bws[mb];
       if (bw > 64) return false;
       mb_bytes = (int64_t)bw * mb_vals / 8;
-      if (p + mb_bytes > pend) return false;
+      if (mb_bytes > pend - p) return false;
     }
     u64 d = 0;
     if (bw) {
@@ -5216,7 +5208,8 @@ struct DbpStream {
       if (bw < 64) d &= (1ull << bw) - 1;
     }
     ++t;
-    value += min_delta + (i64)d;
+    // the spec's arithmetic wraps: add in u64, signed overflow is undefined
+    value = (i64)((u64)value + (u64)min_delta + d);
     ++produced;
     return true;
   }
@@ -5237,8 +5230,8 @@ __device__ void k_delta_bp_body(const bg_delta_bp_job& job, int* err) {
     if (job.page_len < 4) { atomicExch(err, 3); return; }
     const uint32_t dlen = (uint32_t)p[0] | ((uint32_t)p[1] << 8) |
                           ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+    if ((int64_t)dlen > job.page_len - 4) { atomicExch(err, 3); return; }
     p += 4 + dlen;
-    if (p > pend) { atomicExch(err, 3); return; }
   }
   DbpStream st;
   if (!st.init(p, pend)) { atomicExch(err, 3); return; }
@@ -5283,8 +5276,8 @@ __device__ void k_delta_ba_body(const bg_delta_ba_job& job, int pass,
     if (job.page_len < 4) { atomicExch(err, 3); return; }
     const uint32_t dlen = (uint32_t)p[0] | ((uint32_t)p[1] << 8) |
                           ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+    if ((int64_t)dlen > job.page_len - 4) { atomicExch(err, 3); return; }
     p += 4 + dlen;
-    if (p > pend) { atomicExch(err, 3); return; }
   }
   const int64_t want = job.has_def == 2 ? *job.d_n_present : job.nvals;
   if (pass == 1)
@@ -5305,7 +5298,10 @@ __device__ void k_delta_ba_body(const bg_delta_ba_job& job, int pass,
     if (!probe.finish()) { atomicExch(err, 3); return; }
     const uint8_t* bytes = probe.p;
     int64_t slot = 0, cursor = 0;
-    auto emit = [&](i64 ln) {
+    // a negative length, or one past the page's bytes, is rejected before
+    // it reaches the scan in bg_ba_materialize
+    auto emit = [&](i64 ln) -> bool {
+      if (ln < 0 || ln > (pend - bytes) - cursor) return false;
       if (job.has_def == 2)
         while (slot < job.nvals && job.d_vidx[slot] == 0xffffffffu) ++slot;
       if (slot < job.nvals) {
@@ -5314,13 +5310,12 @@ __device__ void k_delta_ba_body(const bg_delta_ba_job& job, int pass,
         ++slot;
       }
       cursor += ln;
+      return true;
     };
-    emit(lens.value);
+    if (!emit(lens.value)) { atomicExch(err, 3); return; }
     for (int64_t k2 = 1; k2 < want; ++k2) {
-      if (!lens.next()) { atomicExch(err, 3); return; }
-      emit(lens.value);
+      if (!lens.next() || !emit(lens.value)) { atomicExch(err, 3); return; }
     }
-    if (bytes + cursor > pend) { atomicExch(err, 3); return; }
     return;
   }
   // enc 7: prefix lens stream, suffix lens stream, suffix bytes
@@ -5345,6 +5340,7 @@ __device__ void k_delta_ba_body(const bg_delta_ba_job& job, int pass,
   bool first = true;
   auto step = [&](i64 plen, i64 slen) -> bool {
     if (plen < 0 || slen < 0) return false;
+    if (slen > (pend - sbytes) - cursor) return false;  // suffix past page
     if (first && plen != 0) return false;  // nothing to prefix from
     if (!first && plen > prev_len) return false;
     if (job.has_def == 2)
@@ -5444,6 +5440,7 @@ __device__ void k_ba_extract_body(const bg_ba_page_job& job, int* err) {
     const uint32_t dlen = (uint32_t)p[0] | ((uint32_t)p[1] << 8) |
                           ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
     pos = 4 + (int64_t)dlen;
+    if (pos > job.page_len) { atomicExch(err, 3); return; }
   }
   for (int64_t s = 0; s < job.nvals; ++s) {
     if (job.has_def == 2 && job.d_vidx[s] == 0xffffffffu) continue;
