@@ -1700,6 +1700,54 @@ static u64 next_pow2_u64(u64 x) {
   return p;
 }
 
+// The chained table of either join handle: mask for the smallest power of
+// two of at least 2n buckets (8 at the least), head[] filled with -1, one
+// node per build row.
+static int join_alloc_table(int64_t n, u64* mask, DevBuf<int>* head,
+                            DevBuf<ulong2>* nodes) {
+  const u64 nb = next_pow2_u64((u64)(n > 4 ? n * 2 : 8));
+  *mask = nb - 1;
+  HIP_TRY(nodes->alloc(n));
+  HIP_TRY(head->alloc((int64_t)nb));
+  HIP_TRY(hipMemset(head->get(), 0xff, sizeof(int) * nb));  // -1
+  return BG_OK;
+}
+
+// The count phase of either join handle once the call is checked:
+// launch(counts) fills one u32 count per probe row, their exclusive scan
+// becomes the offsets the handle keeps for the fill, the total goes to the
+// caller.
+template <typename Table, typename Launch>
+static int join_count_phase(Table* t, int64_t n, int64_t* out_matches,
+                            Launch&& launch) {
+  // release the previous probe's offsets FIRST so the pool can recycle the
+  // buffer for this call (allocating before releasing forces a fresh
+  // multi-GB hipMalloc inside the hot path)
+  if (t->probe_offsets) {
+    (void)pool_release(t->probe_offsets);
+    t->probe_offsets = nullptr;
+  }
+  DevBuf<uint32_t> d_counts;
+  DevBuf<i64> d_offs;
+  DevBuf<i64> d_total;
+  HIP_TRY(d_counts.alloc(n));
+  HIP_TRY(d_offs.alloc(n));
+  HIP_TRY(d_total.alloc(1));
+  launch(d_counts.get());
+  HIP_TRY(hipGetLastError());
+  // u32 counts: chains are < 2^31 long and per-row match counts fit —
+  // halves the count write and the scan's level-0/3 read traffic
+  int rc = scan_exclusive_u32(d_counts, n, d_offs, d_total);
+  if (rc != BG_OK) return rc;
+  i64 total = 0;
+  HIP_TRY(hipMemcpy(&total, d_total, sizeof(i64), hipMemcpyDeviceToHost));
+  // the handle owns the offsets until the next count or its free
+  t->probe_offsets = d_offs.detach();
+  t->probe_n = n;
+  *out_matches = total;
+  return BG_OK;
+}
+
 extern "C" int bg_hashjoin_build(const bg_column* build_keys, int64_t n,
                                  void** out_handle) {
   REQUIRE_INIT();
@@ -1708,13 +1756,10 @@ extern "C" int bg_hashjoin_build(const bg_column* build_keys, int64_t n,
   if (n > 0x7fffffffLL) return set_err(BG_ERR_INVALID, "build side > 2^31 rows");
   BgJoinTable t{};
   t.n_build = n;
-  const u64 nb = next_pow2_u64((u64)(n > 4 ? n * 2 : 8));
-  t.mask = nb - 1;
   DevBuf<ulong2> nodes;
   DevBuf<int> head;
-  HIP_TRY(nodes.alloc(n));
-  HIP_TRY(head.alloc((int64_t)nb));
-  HIP_TRY(hipMemset(head, 0xff, sizeof(int) * nb));  // -1
+  int rc = join_alloc_table(n, &t.mask, &head, &nodes);
+  if (rc != BG_OK) return rc;
   int blocks = grid_for(n);
   hipLaunchKernelGGL(k_join_build, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      (const int64_t*)build_keys->d_data,
@@ -1735,37 +1780,12 @@ extern "C" int bg_hashjoin_probe_count(void* handle,
   BgJoinTable* t = (BgJoinTable*)handle;
   if (probe_keys->dtype != BG_DT_INT64)
     return set_err(BG_ERR_UNSUPPORTED, "join keys must be INT64 (round 1)");
-  // release the previous probe's offsets FIRST so the pool can recycle the
-  // buffer for this call (allocating before releasing forces a fresh
-  // multi-GB hipMalloc inside the hot path)
-  if (t->probe_offsets) {
-    (void)pool_release(t->probe_offsets);
-    t->probe_offsets = nullptr;
-  }
-  DevBuf<uint32_t> d_counts;
-  DevBuf<i64> d_offs;
-  DevBuf<i64> d_total;
-  HIP_TRY(d_counts.alloc(n));
-  HIP_TRY(d_offs.alloc(n));
-  HIP_TRY(d_total.alloc(1));
-  int blocks = grid_for(n);
-  hipLaunchKernelGGL(k_join_count, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                     (const int64_t*)probe_keys->d_data,
-                     probe_keys->d_validity, n, t->head, t->nodes,
-                     t->mask, d_counts);
-  {
-    // u32 counts: chains are < 2^31 long and per-row match counts fit —
-    // halves the count write and the scan's level-0/3 read traffic
-    int rc = scan_exclusive_u32(d_counts, n, d_offs, d_total);
-    if (rc != BG_OK) return rc;
-  }
-  i64 total = 0;
-  HIP_TRY(hipMemcpy(&total, d_total, sizeof(i64), hipMemcpyDeviceToHost));
-  // stash offsets on the handle for the fill call
-  t->probe_offsets = d_offs.detach();
-  t->probe_n = n;
-  *out_matches = total;
-  return BG_OK;
+  return join_count_phase(t, n, out_matches, [&](uint32_t* d_counts) {
+    hipLaunchKernelGGL(k_join_count, dim3(grid_for(n)), dim3(BG_BLOCK), 0, 0,
+                       (const int64_t*)probe_keys->d_data,
+                       probe_keys->d_validity, n, t->head, t->nodes, t->mask,
+                       d_counts);
+  });
 }
 
 extern "C" int bg_hashjoin_probe_fill(void* handle,
@@ -6857,74 +6877,6 @@ __global__ void k_join_build2(KeyArgs keys, int64_t n, int* head,
   }
 }
 
-__global__ void k_join_count2(KeyArgs bkeys, KeyArgs pkeys, int64_t n_probe,
-                              const int* head, const ulong2* nodes, u64 mask,
-                              int32_t join_type, uint32_t* counts) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n_probe; i += (int64_t)gridDim.x * blockDim.x) {
-    u64 cnt = 0;
-    if (!row_has_null_key(pkeys, i)) {
-      const u64 h = hash_keys_row(pkeys, i);
-      int64_t cur = head[h & mask];
-      while (cur >= 0) {
-        const ulong2 node = nodes[cur];
-        if (node.x == h && keys_equal_cross(bkeys, cur, pkeys, i)) {
-          ++cnt;
-          if (join_type == BG_JOIN_SEMI || join_type == BG_JOIN_ANTI) break;
-        }
-        cur = (int64_t)node.y;
-      }
-    }
-    switch (join_type) {
-      case BG_JOIN_INNER: break;
-      case BG_JOIN_SEMI: cnt = cnt ? 1 : 0; break;
-      case BG_JOIN_ANTI: cnt = cnt ? 0 : 1; break;
-      case BG_JOIN_OUTER_PROBE: cnt = cnt ? cnt : 1; break;
-      default: break;
-    }
-    counts[i] = (uint32_t)cnt;
-  }
-}
-
-__global__ void k_join_fill2(KeyArgs bkeys, KeyArgs pkeys, int64_t n_probe,
-                             const int* head, const ulong2* nodes, u64 mask,
-                             int32_t join_type, const i64* offsets,
-                             uint32_t* out_probe, uint32_t* out_build) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n_probe; i += (int64_t)gridDim.x * blockDim.x) {
-    i64 w = offsets[i];
-    u64 matched = 0;
-    if (!row_has_null_key(pkeys, i)) {
-      const u64 h = hash_keys_row(pkeys, i);
-      int64_t cur = head[h & mask];
-      while (cur >= 0) {
-        const ulong2 node = nodes[cur];
-        if (node.x == h && keys_equal_cross(bkeys, cur, pkeys, i)) {
-          ++matched;
-          if (join_type == BG_JOIN_SEMI) {
-            out_probe[w] = (uint32_t)i;
-            out_build[w] = (uint32_t)cur;
-            ++w;
-            break;
-          }
-          if (join_type == BG_JOIN_ANTI) break;
-          if (join_type != BG_JOIN_ANTI) {
-            out_probe[w] = (uint32_t)i;
-            out_build[w] = (uint32_t)cur;
-            ++w;
-          }
-        }
-        cur = (int64_t)node.y;
-      }
-    }
-    if (!matched &&
-        (join_type == BG_JOIN_ANTI || join_type == BG_JOIN_OUTER_PROBE)) {
-      out_probe[w] = (uint32_t)i;
-      out_build[w] = BG_JOIN_NULL_IDX;
-    }
-  }
-}
-
 // Build-side-preserving types (DataFusion's LeftSemi/LeftAnti/Left/Full,
 // build = its left input): one visited bit per build row, Arrow LSB order,
 // set by every probe row that matches it.  The plain load in front of the
@@ -6938,60 +6890,6 @@ __device__ __forceinline__ void mark_visited(uint32_t* words, int64_t row) {
   if (!(*w & bit)) atomicOr(w, bit);  // result unused: no-return form
 }
 
-// k_join_count2's chain walk, run to the chain's end: every build row
-// with an equal key is marked, nothing is emitted
-__global__ void k_join_mark2(KeyArgs bkeys, KeyArgs pkeys, int64_t n_probe,
-                             const int* head, const ulong2* nodes, u64 mask,
-                             uint32_t* visited) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n_probe; i += (int64_t)gridDim.x * blockDim.x) {
-    if (row_has_null_key(pkeys, i)) continue;
-    const u64 h = hash_keys_row(pkeys, i);
-    int64_t cur = head[h & mask];
-    while (cur >= 0) {
-      const ulong2 node = nodes[cur];
-      if (node.x == h && keys_equal_cross(bkeys, cur, pkeys, i))
-        mark_visited(visited, cur);
-      cur = (int64_t)node.y;
-    }
-  }
-}
-
-// k_join_fill2 for BG_JOIN_OUTER_BUILD (pairs as INNER) and
-// BG_JOIN_OUTER_FULL (pairs as OUTER_PROBE), marking each matched build
-// row.  A kernel of its own, so k_join_fill2 stays as it was.
-__global__ void k_join_fill_mark2(KeyArgs bkeys, KeyArgs pkeys,
-                                  int64_t n_probe, const int* head,
-                                  const ulong2* nodes, u64 mask,
-                                  int32_t keep_unmatched_probe,
-                                  const i64* offsets, uint32_t* out_probe,
-                                  uint32_t* out_build, uint32_t* visited) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n_probe; i += (int64_t)gridDim.x * blockDim.x) {
-    i64 w = offsets[i];
-    bool matched = false;
-    if (!row_has_null_key(pkeys, i)) {
-      const u64 h = hash_keys_row(pkeys, i);
-      int64_t cur = head[h & mask];
-      while (cur >= 0) {
-        const ulong2 node = nodes[cur];
-        if (node.x == h && keys_equal_cross(bkeys, cur, pkeys, i)) {
-          matched = true;
-          out_probe[w] = (uint32_t)i;
-          out_build[w] = (uint32_t)cur;
-          ++w;
-          mark_visited(visited, cur);
-        }
-        cur = (int64_t)node.y;
-      }
-    }
-    if (!matched && keep_unmatched_probe) {
-      out_probe[w] = (uint32_t)i;
-      out_build[w] = BG_JOIN_NULL_IDX;
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------
 // Join residual filters (HashJoinExec with filter: Some(JoinFilter);
 // approved/q21.txt:60-61, q7.txt, q19.txt).  The filter decides which
@@ -7001,7 +6899,8 @@ __global__ void k_join_fill_mark2(KeyArgs bkeys, KeyArgs pkeys,
 // caller evaluated the single-side predicates into them) and up to four
 // build-column <cmp> probe-column compares.  The program travels as a
 // kernel argument like KeyArgs; every loop bound over it is wave-uniform.
-// Kernels of their own, so the unfiltered ones above stay as they were.
+// The probe kernels below take it through a filter policy, so the filtered
+// and the unfiltered probe are two instantiations of one chain walk.
 // ---------------------------------------------------------------------------
 struct JoinFilterArgs {
   int ngroups;
@@ -7065,10 +6964,10 @@ __device__ __forceinline__ uint32_t jf_live_groups(const JoinFilterArgs& f,
   return live;
 }
 
-// THE decision "candidate (build row b, probe row p) passes": the count,
-// fill and mark walks all call it, so they cannot disagree (count sizes the
-// slots fill writes into).  First failing term ends a group, first passing
-// group ends the test.
+// THE decision "candidate (build row b, probe row p) passes", called from
+// the one chain walk (join_walk) that count, fill and mark share, so they
+// cannot disagree (count sizes the slots fill writes into).  First failing
+// term ends a group, first passing group ends the test.
 __device__ __forceinline__ bool jf_candidate_passes(const JoinFilterArgs& f,
                                                     uint32_t live, int64_t b,
                                                     int64_t p) {
@@ -7082,100 +6981,127 @@ __device__ __forceinline__ bool jf_candidate_passes(const JoinFilterArgs& f,
   return false;
 }
 
-// k_join_count2 over passing candidates.  A probe row with no live group
-// skips the hash and the walk.
-__global__ void k_join_count2f(KeyArgs bkeys, KeyArgs pkeys, int64_t n_probe,
-                               const int* head, const ulong2* nodes, u64 mask,
-                               int32_t join_type, JoinFilterArgs f,
-                               uint32_t* counts) {
+// Filter policies of the chain walk.  live(p): the groups probe row p can
+// still pass in, 0 = skip the row; passes(live, b, p): candidate (b, p)
+// counts as a match.  JoinNoFilter is empty, so the unfiltered kernels carry
+// no JoinFilterArgs in their argument block.
+struct JoinNoFilter {
+  __device__ __forceinline__ uint32_t live(int64_t) const { return 1; }
+  __device__ __forceinline__ bool passes(uint32_t, int64_t, int64_t) const {
+    return true;
+  }
+};
+struct JoinFiltered {
+  JoinFilterArgs f;
+  __device__ __forceinline__ uint32_t live(int64_t p) const {
+    return jf_live_groups(f, p);
+  }
+  __device__ __forceinline__ bool passes(uint32_t live, int64_t b,
+                                         int64_t p) const {
+    return jf_candidate_passes(f, live, b, p);
+  }
+};
+
+// The table a probe kernel walks and the probe rows it walks it for.
+struct JoinProbeArgs {
+  KeyArgs bkeys, pkeys;
+  int64_t n_probe;
+  const int* head;
+  const ulong2* nodes;
+  u64 mask;
+};
+
+// THE chain walk of probe row i: calls match(build row) for every build row
+// with an equal key that the filter passes, in chain order, until match
+// returns true ("stop").  A probe row with no live group or with a NULL key
+// matches nothing and is neither hashed nor walked.  Count, fill and mark
+// all go through here, so they see the same matches in the same order.
+// The stop flag in the loop condition, not an early return, is deliberate:
+// with a return the unfiltered fill compiles to 106 SGPRs and 7 waves, with
+// the flag to 100 and 8 (profiles/kernel_resource_usage_join_probe.txt).
+template <typename Filter, typename Match>
+__device__ __forceinline__ void join_walk(const JoinProbeArgs& t,
+                                          const Filter& f, int64_t i,
+                                          Match&& match) {
+  const uint32_t live = f.live(i);
+  if (!live || row_has_null_key(t.pkeys, i)) return;
+  const u64 h = hash_keys_row(t.pkeys, i);
+  int64_t cur = t.head[h & t.mask];
+  bool stop = false;
+  while (cur >= 0 && !stop) {
+    const ulong2 node = t.nodes[cur];
+    if (node.x == h && keys_equal_cross(t.bkeys, cur, t.pkeys, i) &&
+        f.passes(live, cur, i))
+      stop = match(cur);
+    cur = (int64_t)node.y;
+  }
+}
+
+// What the four pair-emitting types do with a probe row (join_pair_type
+// maps the marking types onto them before a launch).  The count and the fill
+// both read these, so the fill writes exactly the slots the count sized.
+__device__ __forceinline__ bool join_first_match_decides(int32_t jt) {
+  return jt == BG_JOIN_SEMI || jt == BG_JOIN_ANTI;
+}
+__device__ __forceinline__ bool join_emits_matches(int32_t jt) {
+  return jt != BG_JOIN_ANTI;
+}
+__device__ __forceinline__ bool join_emits_unmatched_probe(int32_t jt) {
+  return jt == BG_JOIN_ANTI || jt == BG_JOIN_OUTER_PROBE;
+}
+
+template <typename Filter>
+__global__ void k_join_count2(JoinProbeArgs t, int32_t join_type, Filter f,
+                              uint32_t* counts) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n_probe; i += (int64_t)gridDim.x * blockDim.x) {
+       i < t.n_probe; i += (int64_t)gridDim.x * blockDim.x) {
     u64 cnt = 0;
-    const uint32_t live = jf_live_groups(f, i);
-    if (live && !row_has_null_key(pkeys, i)) {
-      const u64 h = hash_keys_row(pkeys, i);
-      int64_t cur = head[h & mask];
-      while (cur >= 0) {
-        const ulong2 node = nodes[cur];
-        if (node.x == h && keys_equal_cross(bkeys, cur, pkeys, i) &&
-            jf_candidate_passes(f, live, cur, i)) {
-          ++cnt;
-          if (join_type == BG_JOIN_SEMI || join_type == BG_JOIN_ANTI) break;
-        }
-        cur = (int64_t)node.y;
-      }
-    }
-    switch (join_type) {
-      case BG_JOIN_INNER: break;
-      case BG_JOIN_SEMI: cnt = cnt ? 1 : 0; break;
-      case BG_JOIN_ANTI: cnt = cnt ? 0 : 1; break;
-      case BG_JOIN_OUTER_PROBE: cnt = cnt ? cnt : 1; break;
-      default: break;
-    }
+    join_walk(t, f, i, [&](int64_t) {
+      ++cnt;
+      return join_first_match_decides(join_type);
+    });
+    if (!join_emits_matches(join_type)) cnt = cnt ? 0 : 1;
+    else if (join_emits_unmatched_probe(join_type)) cnt = cnt ? cnt : 1;
     counts[i] = (uint32_t)cnt;
   }
 }
 
-// k_join_fill2 (MARK=false: INNER/SEMI/ANTI/OUTER_PROBE) and
-// k_join_fill_mark2 (MARK=true: INNER or OUTER_PROBE pairs, each passing
-// candidate's build row marked) over passing candidates; writes exactly the
-// slots k_join_count2f counted for the same join_type and filter.
-template <bool MARK>
-__global__ void k_join_fill2f(KeyArgs bkeys, KeyArgs pkeys, int64_t n_probe,
-                              const int* head, const ulong2* nodes, u64 mask,
-                              int32_t join_type, JoinFilterArgs f,
-                              const i64* offsets, uint32_t* out_probe,
-                              uint32_t* out_build, uint32_t* visited) {
+// Writes the pairs k_join_count2 counted for the same join_type and filter.
+// MARK also marks every matched build row; it is launched for INNER and
+// OUTER_PROBE pairs only, so the first-match types compile out of it.
+template <typename Filter, bool MARK>
+__global__ void k_join_fill2(JoinProbeArgs t, int32_t join_type, Filter f,
+                             const i64* offsets, uint32_t* out_probe,
+                             uint32_t* out_build, uint32_t* visited) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n_probe; i += (int64_t)gridDim.x * blockDim.x) {
+       i < t.n_probe; i += (int64_t)gridDim.x * blockDim.x) {
     i64 w = offsets[i];
     bool matched = false;
-    const uint32_t live = jf_live_groups(f, i);
-    if (live && !row_has_null_key(pkeys, i)) {
-      const u64 h = hash_keys_row(pkeys, i);
-      int64_t cur = head[h & mask];
-      while (cur >= 0) {
-        const ulong2 node = nodes[cur];
-        if (node.x == h && keys_equal_cross(bkeys, cur, pkeys, i) &&
-            jf_candidate_passes(f, live, cur, i)) {
-          matched = true;
-          if (join_type != BG_JOIN_ANTI) {
-            out_probe[w] = (uint32_t)i;
-            out_build[w] = (uint32_t)cur;
-            ++w;
-          }
-          if (MARK) mark_visited(visited, cur);
-          if (join_type == BG_JOIN_SEMI || join_type == BG_JOIN_ANTI) break;
-        }
-        cur = (int64_t)node.y;
-      }
-    }
-    if (!matched &&
-        (join_type == BG_JOIN_ANTI || join_type == BG_JOIN_OUTER_PROBE)) {
+    join_walk(t, f, i, [&](int64_t b) {
+      matched = true;
+      if (MARK) mark_visited(visited, b);
+      if (!MARK && !join_emits_matches(join_type)) return true;
+      out_probe[w] = (uint32_t)i;
+      out_build[w] = (uint32_t)b;
+      ++w;
+      return !MARK && join_first_match_decides(join_type);
+    });
+    if (!matched && join_emits_unmatched_probe(join_type)) {
       out_probe[w] = (uint32_t)i;
       out_build[w] = BG_JOIN_NULL_IDX;
     }
   }
 }
 
-// k_join_mark2 over passing candidates: walks to the chain's end
-__global__ void k_join_mark2f(KeyArgs bkeys, KeyArgs pkeys, int64_t n_probe,
-                              const int* head, const ulong2* nodes, u64 mask,
-                              JoinFilterArgs f, uint32_t* visited) {
+// Marks every matched build row and emits nothing: walks to the chain's end.
+template <typename Filter>
+__global__ void k_join_mark2(JoinProbeArgs t, Filter f, uint32_t* visited) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n_probe; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint32_t live = jf_live_groups(f, i);
-    if (!live || row_has_null_key(pkeys, i)) continue;
-    const u64 h = hash_keys_row(pkeys, i);
-    int64_t cur = head[h & mask];
-    while (cur >= 0) {
-      const ulong2 node = nodes[cur];
-      if (node.x == h && keys_equal_cross(bkeys, cur, pkeys, i) &&
-          jf_candidate_passes(f, live, cur, i))
-        mark_visited(visited, cur);
-      cur = (int64_t)node.y;
-    }
-  }
+       i < t.n_probe; i += (int64_t)gridDim.x * blockDim.x)
+    join_walk(t, f, i, [&](int64_t b) {
+      mark_visited(visited, b);
+      return false;
+    });
 }
 
 // ~visited (or all ones where nothing was ever marked) as a mask for the
@@ -7247,20 +7173,52 @@ static int join_ensure_visited(BgJoinTable2* t) {
 // probe keys checked against the handle's build keys
 static int join_probe_keys(const BgJoinTable2* t, const bg_column* keys,
                            int32_t nkeys, KeyArgs* pk) {
-  if (keyargs_from_cols(keys, nkeys, pk) != BG_OK || nkeys != t->nkeys)
-    return set_err(BG_ERR_UNSUPPORTED, "probe key dtype/count mismatch");
-  for (int c = 0; c < nkeys; ++c)
-    if (pk->k[c].dtype != t->bkeys.k[c].dtype)
-      return set_err(BG_ERR_INVALID, "probe/build key dtypes differ");
+  if (nkeys != t->nkeys)
+    return set_err(BG_ERR_INVALID, "probe/build key counts differ");
+  // a dtype keyargs_from_cols refuses is none of the build's either
+  bool same = keyargs_from_cols(keys, nkeys, pk) == BG_OK;
+  for (int c = 0; same && c < nkeys; ++c)
+    same = pk->k[c].dtype == t->bkeys.k[c].dtype;
+  if (!same) return set_err(BG_ERR_INVALID, "probe/build key dtypes differ");
   return BG_OK;
 }
 
-// SEMI_BUILD / ANTI_BUILD emit build rows, never pairs
-static int join_refuse_pairless(int32_t jt) {
-  if (jt != BG_JOIN_SEMI_BUILD && jt != BG_JOIN_ANTI_BUILD) return BG_OK;
-  return set_err(BG_ERR_INVALID,
-                 "SEMI_BUILD/ANTI_BUILD emit no pairs: call "
-                 "bg_hashjoin_probe_mark2, then bg_hashjoin_build_rows2");
+// What every general probe entry checks first, before anything is allocated
+// or launched: the handle, and the probe keys against the build's.  -> the
+// kernels' view of the table and of this call's probe rows.
+static int join_probe_args(void* handle, const bg_column* keys, int32_t nkeys,
+                           int64_t n, JoinProbeArgs* a) {
+  const BgJoinTable2* t = (const BgJoinTable2*)handle;
+  if (!t) return set_err(BG_ERR_INVALID, "null join handle");
+  a->bkeys = t->bkeys;
+  a->n_probe = n;
+  a->head = t->head;
+  a->nodes = t->nodes;
+  a->mask = t->mask;
+  return join_probe_keys(t, keys, nkeys, &a->pkeys);
+}
+
+// The count and fill entries take the pair-emitting types only: SEMI_BUILD /
+// ANTI_BUILD emit build rows, never pairs.
+static int join_check_pair_type(int32_t jt) {
+  if (jt == BG_JOIN_SEMI_BUILD || jt == BG_JOIN_ANTI_BUILD)
+    return set_err(BG_ERR_INVALID,
+                   "SEMI_BUILD/ANTI_BUILD emit no pairs: call "
+                   "bg_hashjoin_probe_mark2, then bg_hashjoin_build_rows2");
+  if (jt < BG_JOIN_INNER || jt > BG_JOIN_OUTER_FULL)
+    return set_err(BG_ERR_INVALID, "unknown join_type");
+  return BG_OK;
+}
+
+// The marking types emit the pairs of the type they extend: OUTER_BUILD
+// pairs as INNER, OUTER_FULL pairs as OUTER_PROBE.
+static int32_t join_pair_type(int32_t jt) {
+  return jt == BG_JOIN_OUTER_BUILD  ? BG_JOIN_INNER
+         : jt == BG_JOIN_OUTER_FULL ? BG_JOIN_OUTER_PROBE
+                                    : jt;
+}
+static bool join_type_marks(int32_t jt) {
+  return jt == BG_JOIN_OUTER_BUILD || jt == BG_JOIN_OUTER_FULL;
 }
 
 extern "C" int bg_hashjoin_build2(const bg_column* keys, int32_t nkeys,
@@ -7273,13 +7231,10 @@ extern "C" int bg_hashjoin_build2(const bg_column* keys, int32_t nkeys,
     return set_err(BG_ERR_UNSUPPORTED, "join key dtype/count unsupported");
   t.nkeys = nkeys;
   t.n_build = n;
-  const u64 nb = next_pow2_u64((u64)(n > 4 ? n * 2 : 8));
-  t.mask = nb - 1;
   DevBuf<ulong2> nodes;
   DevBuf<int> head;
-  HIP_TRY(nodes.alloc(n));
-  HIP_TRY(head.alloc((int64_t)nb));
-  HIP_TRY(hipMemset(head, 0xff, sizeof(int) * nb));
+  int rc = join_alloc_table(n, &t.mask, &head, &nodes);
+  if (rc != BG_OK) return rc;
   int blocks = grid_for(n);
   hipLaunchKernelGGL(k_join_build2, dim3(blocks), dim3(BG_BLOCK), 0, 0,
                      t.bkeys, n, head.get(), nodes.get(), t.mask);
@@ -7288,81 +7243,6 @@ extern "C" int bg_hashjoin_build2(const bg_column* keys, int32_t nkeys,
   t.nodes = nodes.detach();
   t.head = head.detach();
   *out_handle = new BgJoinTable2(t);
-  return BG_OK;
-}
-
-extern "C" int bg_hashjoin_probe_count2(void* handle, const bg_column* keys,
-                                        int32_t nkeys, int64_t n,
-                                        int32_t join_type,
-                                        int64_t* out_matches) {
-  REQUIRE_INIT();
-  BgJoinTable2* t = (BgJoinTable2*)handle;
-  KeyArgs pk;
-  int krc = join_probe_keys(t, keys, nkeys, &pk);
-  if (krc != BG_OK) return krc;
-  if ((krc = join_refuse_pairless(join_type)) != BG_OK) return krc;
-  // the marking types count pairs exactly as the type they extend
-  const int32_t count_jt = join_type == BG_JOIN_OUTER_BUILD
-                               ? BG_JOIN_INNER
-                               : join_type == BG_JOIN_OUTER_FULL
-                                     ? BG_JOIN_OUTER_PROBE
-                                     : join_type;
-  if (t->probe_offsets) {
-    (void)pool_release(t->probe_offsets);
-    t->probe_offsets = nullptr;
-  }
-  DevBuf<uint32_t> d_counts;
-  DevBuf<i64> d_offs;
-  DevBuf<i64> d_total;
-  HIP_TRY(d_counts.alloc(n));
-  HIP_TRY(d_offs.alloc(n));
-  HIP_TRY(d_total.alloc(1));
-  int blocks = grid_for(n);
-  hipLaunchKernelGGL(k_join_count2, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                     t->bkeys, pk, n, t->head, t->nodes, t->mask, count_jt,
-                     d_counts);
-  HIP_TRY(hipGetLastError());
-  int rc = scan_exclusive_u32(d_counts, n, d_offs, d_total);
-  if (rc != BG_OK) return rc;
-  i64 total = 0;
-  HIP_TRY(hipMemcpy(&total, d_total, sizeof(i64), hipMemcpyDeviceToHost));
-  t->probe_offsets = d_offs.detach();  // the handle owns it until free2
-  t->probe_n = n;
-  t->probe_jt = join_type;
-  *out_matches = total;
-  return BG_OK;
-}
-
-extern "C" int bg_hashjoin_probe_fill2(void* handle, const bg_column* keys,
-                                       int32_t nkeys, int64_t n,
-                                       int32_t join_type,
-                                       uint32_t* d_out_probe,
-                                       uint32_t* d_out_build) {
-  REQUIRE_INIT();
-  BgJoinTable2* t = (BgJoinTable2*)handle;
-  KeyArgs pk;
-  if (keyargs_from_cols(keys, nkeys, &pk) != BG_OK)
-    return set_err(BG_ERR_UNSUPPORTED, "probe key dtype/count mismatch");
-  if (int rrc = join_refuse_pairless(join_type)) return rrc;
-  if (!t->probe_offsets || t->probe_n != n || t->probe_jt != join_type)
-    return set_err(BG_ERR_INVALID,
-                   "call bg_hashjoin_probe_count2 first (same join_type)");
-  int blocks = grid_for(n);
-  if (join_type == BG_JOIN_OUTER_BUILD || join_type == BG_JOIN_OUTER_FULL) {
-    int rc = join_ensure_visited(t);
-    if (rc != BG_OK) return rc;
-    hipLaunchKernelGGL(k_join_fill_mark2, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                       t->bkeys, pk, n, t->head, t->nodes, t->mask,
-                       join_type == BG_JOIN_OUTER_FULL ? 1 : 0,
-                       t->probe_offsets, d_out_probe, d_out_build,
-                       t->visited);
-    HIP_TRY(hipGetLastError());
-    return BG_OK;
-  }
-  hipLaunchKernelGGL(k_join_fill2, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                     t->bkeys, pk, n, t->head, t->nodes, t->mask, join_type,
-                     t->probe_offsets, d_out_probe, d_out_build);
-  HIP_TRY(hipGetLastError());
   return BG_OK;
 }
 
@@ -7375,24 +7255,6 @@ extern "C" int bg_hashjoin_free2(void* handle) {
   if (t->probe_offsets) (void)pool_release(t->probe_offsets);
   if (t->visited) (void)pool_release(t->visited);
   delete t;
-  return BG_OK;
-}
-
-extern "C" int bg_hashjoin_probe_mark2(void* handle, const bg_column* keys,
-                                       int32_t nkeys, int64_t n) {
-  REQUIRE_INIT();
-  BgJoinTable2* t = (BgJoinTable2*)handle;
-  if (!t) return set_err(BG_ERR_INVALID, "null join handle");
-  KeyArgs pk;
-  int rc = join_probe_keys(t, keys, nkeys, &pk);
-  if (rc != BG_OK) return rc;
-  rc = join_ensure_visited(t);
-  if (rc != BG_OK) return rc;
-  if (n <= 0) return BG_OK;
-  int blocks = grid_for(n);
-  hipLaunchKernelGGL(k_join_mark2, dim3(blocks), dim3(BG_BLOCK), 0, 0,
-                     t->bkeys, pk, n, t->head, t->nodes, t->mask, t->visited);
-  HIP_TRY(hipGetLastError());
   return BG_OK;
 }
 
@@ -7490,52 +7352,121 @@ static int join_filter_args(const bg_join_filter_term* terms, int32_t nterms,
   return BG_OK;
 }
 
+// run(policy) with the walk's filter policy for an optional filter
+template <typename Run>
+static void join_with_filter(const JoinFilterArgs* f, Run&& run) {
+  if (f) run(JoinFiltered{*f});
+  else run(JoinNoFilter{});
+}
+
+// Count, fill and mark of a checked call; f is null without a filter.
+static int join_count(BgJoinTable2* t, const JoinProbeArgs& a,
+                      int32_t join_type, const JoinFilterArgs* f,
+                      int64_t* out_matches) {
+  if (!out_matches) return set_err(BG_ERR_INVALID, "null out_matches");
+  int rc = join_count_phase(t, a.n_probe, out_matches, [&](uint32_t* counts) {
+    join_with_filter(f, [&](auto filter) {
+      hipLaunchKernelGGL(k_join_count2<decltype(filter)>,
+                         dim3(grid_for(a.n_probe)), dim3(BG_BLOCK), 0, 0, a,
+                         join_pair_type(join_type), filter, counts);
+    });
+  });
+  if (rc != BG_OK) return rc;
+  // a fill must repeat the type and, with JOIN_JT_FILTERED, the filter
+  t->probe_jt = f ? join_type | JOIN_JT_FILTERED : join_type;
+  if (f) t->probe_filter = *f;
+  return BG_OK;
+}
+
+static int join_fill(BgJoinTable2* t, const JoinProbeArgs& a,
+                     int32_t join_type, const JoinFilterArgs* f,
+                     uint32_t* d_out_probe, uint32_t* d_out_build) {
+  // the offsets are only good for the type and filter they were counted under
+  if (!t->probe_offsets || t->probe_n != a.n_probe ||
+      t->probe_jt != (f ? join_type | JOIN_JT_FILTERED : join_type) ||
+      (f && memcmp(f, &t->probe_filter, sizeof(*f)) != 0))
+    return set_err(BG_ERR_INVALID,
+                   f ? "call bg_hashjoin_probe_count2_filtered first (same "
+                       "join_type, same terms)"
+                     : "call bg_hashjoin_probe_count2 first (same join_type)");
+  const bool mark = join_type_marks(join_type);
+  if (mark) {
+    int rc = join_ensure_visited(t);
+    if (rc != BG_OK) return rc;
+  }
+  join_with_filter(f, [&](auto filter) {
+    using F = decltype(filter);
+    hipLaunchKernelGGL((mark ? k_join_fill2<F, true> : k_join_fill2<F, false>),
+                       dim3(grid_for(a.n_probe)), dim3(BG_BLOCK), 0, 0, a,
+                       join_pair_type(join_type), filter, t->probe_offsets,
+                       d_out_probe, d_out_build, t->visited);
+  });
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+static int join_mark(BgJoinTable2* t, const JoinProbeArgs& a,
+                     const JoinFilterArgs* f) {
+  int rc = join_ensure_visited(t);
+  if (rc != BG_OK) return rc;
+  if (a.n_probe <= 0) return BG_OK;
+  join_with_filter(f, [&](auto filter) {
+    hipLaunchKernelGGL(k_join_mark2<decltype(filter)>,
+                       dim3(grid_for(a.n_probe)), dim3(BG_BLOCK), 0, 0, a,
+                       filter, t->visited);
+  });
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+extern "C" int bg_hashjoin_probe_count2(void* handle, const bg_column* keys,
+                                        int32_t nkeys, int64_t n,
+                                        int32_t join_type,
+                                        int64_t* out_matches) {
+  REQUIRE_INIT();
+  JoinProbeArgs a;
+  int rc = join_probe_args(handle, keys, nkeys, n, &a);
+  if (rc == BG_OK) rc = join_check_pair_type(join_type);
+  if (rc != BG_OK) return rc;
+  return join_count((BgJoinTable2*)handle, a, join_type, nullptr, out_matches);
+}
+
+extern "C" int bg_hashjoin_probe_fill2(void* handle, const bg_column* keys,
+                                       int32_t nkeys, int64_t n,
+                                       int32_t join_type,
+                                       uint32_t* d_out_probe,
+                                       uint32_t* d_out_build) {
+  REQUIRE_INIT();
+  JoinProbeArgs a;
+  int rc = join_probe_args(handle, keys, nkeys, n, &a);
+  if (rc == BG_OK) rc = join_check_pair_type(join_type);
+  if (rc != BG_OK) return rc;
+  return join_fill((BgJoinTable2*)handle, a, join_type, nullptr, d_out_probe,
+                   d_out_build);
+}
+
+extern "C" int bg_hashjoin_probe_mark2(void* handle, const bg_column* keys,
+                                       int32_t nkeys, int64_t n) {
+  REQUIRE_INIT();
+  JoinProbeArgs a;
+  int rc = join_probe_args(handle, keys, nkeys, n, &a);
+  if (rc != BG_OK) return rc;
+  return join_mark((BgJoinTable2*)handle, a, nullptr);
+}
+
 extern "C" int bg_hashjoin_probe_count2_filtered(
     void* handle, const bg_column* keys, int32_t nkeys, int64_t n,
     int32_t join_type, const bg_join_filter_term* terms, int32_t nterms,
     int64_t* out_matches) {
   REQUIRE_INIT();
   BgJoinTable2* t = (BgJoinTable2*)handle;
-  if (!t || !out_matches)
-    return set_err(BG_ERR_INVALID, "null join handle / out_matches");
-  KeyArgs pk;
-  int rc = join_probe_keys(t, keys, nkeys, &pk);
-  if (rc != BG_OK) return rc;
-  if ((rc = join_refuse_pairless(join_type)) != BG_OK) return rc;
-  if (join_type < BG_JOIN_INNER || join_type > BG_JOIN_OUTER_FULL)
-    return set_err(BG_ERR_INVALID, "unknown join_type");
+  JoinProbeArgs a;
   JoinFilterArgs f;
-  if ((rc = join_filter_args(terms, nterms, t->n_build, n, &f)) != BG_OK) return rc;
-  // the marking types count pairs exactly as the type they extend
-  const int32_t count_jt = join_type == BG_JOIN_OUTER_BUILD
-                               ? BG_JOIN_INNER
-                               : join_type == BG_JOIN_OUTER_FULL
-                                     ? BG_JOIN_OUTER_PROBE
-                                     : join_type;
-  if (t->probe_offsets) {
-    (void)pool_release(t->probe_offsets);
-    t->probe_offsets = nullptr;
-  }
-  DevBuf<uint32_t> d_counts;
-  DevBuf<i64> d_offs;
-  DevBuf<i64> d_total;
-  HIP_TRY(d_counts.alloc(n));
-  HIP_TRY(d_offs.alloc(n));
-  HIP_TRY(d_total.alloc(1));
-  hipLaunchKernelGGL(k_join_count2f, dim3(grid_for(n)), dim3(BG_BLOCK), 0, 0,
-                     t->bkeys, pk, n, t->head, t->nodes, t->mask, count_jt, f,
-                     d_counts.get());
-  HIP_TRY(hipGetLastError());
-  rc = scan_exclusive_u32(d_counts, n, d_offs, d_total);
+  int rc = join_probe_args(handle, keys, nkeys, n, &a);
+  if (rc == BG_OK) rc = join_check_pair_type(join_type);
+  if (rc == BG_OK) rc = join_filter_args(terms, nterms, t->n_build, n, &f);
   if (rc != BG_OK) return rc;
-  i64 total = 0;
-  HIP_TRY(hipMemcpy(&total, d_total, sizeof(i64), hipMemcpyDeviceToHost));
-  t->probe_offsets = d_offs.detach();  // the handle owns it until free2
-  t->probe_n = n;
-  t->probe_jt = join_type | JOIN_JT_FILTERED;
-  t->probe_filter = f;
-  *out_matches = total;
-  return BG_OK;
+  return join_count(t, a, join_type, &f, out_matches);
 }
 
 extern "C" int bg_hashjoin_probe_fill2_filtered(
@@ -7544,37 +7475,13 @@ extern "C" int bg_hashjoin_probe_fill2_filtered(
     uint32_t* d_out_probe, uint32_t* d_out_build) {
   REQUIRE_INIT();
   BgJoinTable2* t = (BgJoinTable2*)handle;
-  if (!t) return set_err(BG_ERR_INVALID, "null join handle");
-  KeyArgs pk;
-  int rc = join_probe_keys(t, keys, nkeys, &pk);
-  if (rc != BG_OK) return rc;
-  if ((rc = join_refuse_pairless(join_type)) != BG_OK) return rc;
+  JoinProbeArgs a;
   JoinFilterArgs f;
-  if ((rc = join_filter_args(terms, nterms, t->n_build, n, &f)) != BG_OK) return rc;
-  // the offsets are only good for the filter they were counted under
-  if (!t->probe_offsets || t->probe_n != n ||
-      t->probe_jt != (join_type | JOIN_JT_FILTERED) ||
-      memcmp(&f, &t->probe_filter, sizeof(f)) != 0)
-    return set_err(BG_ERR_INVALID,
-                   "call bg_hashjoin_probe_count2_filtered first (same "
-                   "join_type, same terms)");
-  const int blocks = grid_for(n);
-  if (join_type == BG_JOIN_OUTER_BUILD || join_type == BG_JOIN_OUTER_FULL) {
-    if ((rc = join_ensure_visited(t)) != BG_OK) return rc;
-    hipLaunchKernelGGL(k_join_fill2f<true>, dim3(blocks), dim3(BG_BLOCK), 0,
-                       0, t->bkeys, pk, n, t->head, t->nodes, t->mask,
-                       join_type == BG_JOIN_OUTER_FULL ? BG_JOIN_OUTER_PROBE
-                                                       : BG_JOIN_INNER,
-                       f, t->probe_offsets, d_out_probe, d_out_build,
-                       t->visited);
-  } else {
-    hipLaunchKernelGGL(k_join_fill2f<false>, dim3(blocks), dim3(BG_BLOCK), 0,
-                       0, t->bkeys, pk, n, t->head, t->nodes, t->mask,
-                       join_type, f, t->probe_offsets, d_out_probe,
-                       d_out_build, (uint32_t*)nullptr);
-  }
-  HIP_TRY(hipGetLastError());
-  return BG_OK;
+  int rc = join_probe_args(handle, keys, nkeys, n, &a);
+  if (rc == BG_OK) rc = join_check_pair_type(join_type);
+  if (rc == BG_OK) rc = join_filter_args(terms, nterms, t->n_build, n, &f);
+  if (rc != BG_OK) return rc;
+  return join_fill(t, a, join_type, &f, d_out_probe, d_out_build);
 }
 
 extern "C" int bg_hashjoin_probe_mark2_filtered(
@@ -7582,19 +7489,12 @@ extern "C" int bg_hashjoin_probe_mark2_filtered(
     const bg_join_filter_term* terms, int32_t nterms) {
   REQUIRE_INIT();
   BgJoinTable2* t = (BgJoinTable2*)handle;
-  if (!t) return set_err(BG_ERR_INVALID, "null join handle");
-  KeyArgs pk;
-  int rc = join_probe_keys(t, keys, nkeys, &pk);
-  if (rc != BG_OK) return rc;
+  JoinProbeArgs a;
   JoinFilterArgs f;
-  if ((rc = join_filter_args(terms, nterms, t->n_build, n, &f)) != BG_OK) return rc;
-  if ((rc = join_ensure_visited(t)) != BG_OK) return rc;
-  if (n <= 0) return BG_OK;
-  hipLaunchKernelGGL(k_join_mark2f, dim3(grid_for(n)), dim3(BG_BLOCK), 0, 0,
-                     t->bkeys, pk, n, t->head, t->nodes, t->mask, f,
-                     t->visited);
-  HIP_TRY(hipGetLastError());
-  return BG_OK;
+  int rc = join_probe_args(handle, keys, nkeys, n, &a);
+  if (rc == BG_OK) rc = join_filter_args(terms, nterms, t->n_build, n, &f);
+  if (rc != BG_OK) return rc;
+  return join_mark(t, a, &f);
 }
 
 // sentinel handling for probe-outer joins: split an index vector carrying

@@ -348,7 +348,12 @@ int bg_hashjoin_free2(void* handle);
  * of INNER / OUTER_PROBE, and fill2 also marks every matched build row;
  * the unmatched build rows come from bg_hashjoin_build_rows2(matched=0)
  * after the last probe chunk.  Types 4 and 5 emit no pairs: count2/fill2
- * refuse them with BG_ERR_INVALID and point at bg_hashjoin_probe_mark2. */
+ * refuse them with BG_ERR_INVALID and point at bg_hashjoin_probe_mark2.
+ * Every probe entry of this family, with or without a filter, refuses with
+ * BG_ERR_INVALID, before anything is allocated or launched: a NULL handle
+ * (bg_hashjoin_free2(NULL) stays BG_OK), probe keys whose count or dtypes
+ * differ from the build's, and, in count and fill, a join_type outside
+ * BG_JOIN_INNER .. BG_JOIN_OUTER_FULL. */
 
 /* HashJoinExec's probe-side pass for LeftSemi/LeftAnti, where only the
  * visited bitmap matters: mark only; emits nothing (types 4/5 need no pair

@@ -22,6 +22,10 @@ plans of a pair alternated run by run in this one process:
                        `ne` filter (what the fused plan runs on).
 Every join feeds a no-group sum+count, so no plan pays for shipping rows to
 the host; the two plans of a pair must report the same count and key sum.
+With --parent-lib every plan and every phase of the breakdown also runs on
+the parent commit's library, alternated run by run with this tree's, and is
+recorded under "parent" next to it: the check that a change to the probe
+kernels left their speed where it was.
 Each timed step runs under its own time limit: a watchdog ends the process
 if one overruns."""
 import argparse
@@ -106,10 +110,18 @@ PAIRS = {
 
 
 class Lib:
-    """The library with the two tables registered."""
+    """One loaded copy of the library with the two tables registered."""
 
-    def __init__(self, tables):
-        self.L = gpu.load_library()
+    def __init__(self, path, tables):
+        if path is None:
+            self.L = gpu.load_library()
+        else:
+            self.L = ctypes.CDLL(path)
+            for name, sig in gpu._SIGNATURES.items():
+                fn = getattr(self.L, name, None)
+                if fn is not None:   # the parent may lack newer entries
+                    fn.restype = gpu._CODES[sig[0]]
+                    fn.argtypes = [gpu._CODES[c] for c in sig[2:]]
         assert self.L.bg_init(0) == 0
         self.hash = self.L.bg_source_hash().decode()
         for name, cols in tables.items():
@@ -140,9 +152,10 @@ class Lib:
         return dt, [int(row[0]), int(row[1])]
 
 
-def abi_breakdown(L, c_custkey, c_x, o_custkey, o_x):
-    """Count + fill of the inner join, seconds per phase (median of REPEATS
-    after one warm-up), on the three probe paths."""
+def abi_breakdown(libs, repeats, c_custkey, c_x, o_custkey, o_x):
+    """Count + fill of the inner join, seconds per phase (median of `repeats`
+    after one warm-up), on the three probe paths; -> {library: {path: ...}},
+    the libraries taking turns run by run."""
     def col(t):
         return (gpu.BgColumn * 1)(gpu.BgColumn(
             gpu.BG_DT_INT64, 0, 0, 0, ctypes.c_void_p(t.data_ptr()), None,
@@ -156,54 +169,68 @@ def abi_breakdown(L, c_custkey, c_x, o_custkey, o_x):
     out_b = torch.empty(n, dtype=torch.int32, device=o_custkey.device)
     m = ctypes.c_int64()
 
-    def ok(rc):
+    def ok(L, rc):
         if rc != 0:
             raise RuntimeError(L.bg_last_error().decode())
 
-    def timed(call):
+    def timed(L, call):
         faulthandler.dump_traceback_later(STEP_LIMIT_S, exit=True)
-        ok(L.bg_synchronize())
+        ok(L, L.bg_synchronize())
         t0 = time.perf_counter()
-        ok(call())
-        ok(L.bg_synchronize())
+        ok(L, call())
+        ok(L, L.bg_synchronize())
         dt = time.perf_counter() - t0
         faulthandler.cancel_dump_traceback_later()
         return dt
 
-    fast, general = ctypes.c_void_p(), ctypes.c_void_p()
-    ok(L.bg_hashjoin_build(bkey, c_custkey.shape[0], ctypes.byref(fast)))
-    ok(L.bg_hashjoin_build2(bkey, 1, c_custkey.shape[0],
-                            ctypes.byref(general)))
     op, ob = out_p.data_ptr(), out_b.data_ptr()
-    paths = {
-        "int64_fast_table": (
-            lambda: L.bg_hashjoin_probe_count(fast, pkey, n, ctypes.byref(m)),
-            lambda: L.bg_hashjoin_probe_fill(fast, pkey, n, op, ob)),
-        "general_table": (
-            lambda: L.bg_hashjoin_probe_count2(general, pkey, 1, n, 0,
-                                               ctypes.byref(m)),
-            lambda: L.bg_hashjoin_probe_fill2(general, pkey, 1, n, 0, op,
-                                              ob)),
-        "general_table_filtered": (
-            lambda: L.bg_hashjoin_probe_count2_filtered(
-                general, pkey, 1, n, 0, term, 1, ctypes.byref(m)),
-            lambda: L.bg_hashjoin_probe_fill2_filtered(
-                general, pkey, 1, n, 0, term, 1, op, ob)),
-    }
-    rec = {}
-    for name, (count, fill) in paths.items():
-        tc, tf = [], []
-        for i in range(REPEATS + 1):
-            c = timed(count)
-            assert 0 < m.value <= n      # the pair buffers hold n pairs
-            f = timed(fill)
-            if i:                        # run 0 warms up
-                tc.append(c)
-                tf.append(f)
-        rec[name] = {"pairs": m.value, "count": spread(tc),
-                     "fill": spread(tf)}
-    ok(L.bg_hashjoin_free(fast))
-    ok(L.bg_hashjoin_free2(general))
+
+    def paths_of(L):
+        fast, general = ctypes.c_void_p(), ctypes.c_void_p()
+        ok(L, L.bg_hashjoin_build(bkey, c_custkey.shape[0],
+                                  ctypes.byref(fast)))
+        ok(L, L.bg_hashjoin_build2(bkey, 1, c_custkey.shape[0],
+                                   ctypes.byref(general)))
+        return fast, general, {
+            "int64_fast_table": (
+                lambda: L.bg_hashjoin_probe_count(fast, pkey, n,
+                                                  ctypes.byref(m)),
+                lambda: L.bg_hashjoin_probe_fill(fast, pkey, n, op, ob)),
+            "general_table": (
+                lambda: L.bg_hashjoin_probe_count2(general, pkey, 1, n, 0,
+                                                   ctypes.byref(m)),
+                lambda: L.bg_hashjoin_probe_fill2(general, pkey, 1, n, 0, op,
+                                                  ob)),
+            "general_table_filtered": (
+                lambda: L.bg_hashjoin_probe_count2_filtered(
+                    general, pkey, 1, n, 0, term, 1, ctypes.byref(m)),
+                lambda: L.bg_hashjoin_probe_fill2_filtered(
+                    general, pkey, 1, n, 0, term, 1, op, ob)),
+        }
+
+    tables = {k: paths_of(lib.L) for k, lib in libs.items()}
+    rec = {k: {} for k in libs}
+    for name in next(iter(tables.values()))[2]:
+        tc, tf = {k: [] for k in libs}, {k: [] for k in libs}
+        pairs = {}
+        for i in range(repeats + 1):
+            turn = list(libs.items())        # alternated, first one too
+            for k, lib in turn[::-1] if i % 2 else turn:
+                count, fill = tables[k][2][name]
+                c = timed(lib.L, count)
+                assert 0 < m.value <= n      # the pair buffers hold n pairs
+                pairs[k] = m.value
+                f = timed(lib.L, fill)
+                if i:                        # run 0 warms up
+                    tc[k].append(c)
+                    tf[k].append(f)
+        assert len(set(pairs.values())) == 1, pairs
+        for k in libs:
+            rec[k][name] = {"pairs": pairs[k], "count": spread(tc[k]),
+                            "fill": spread(tf[k])}
+    for k, lib in libs.items():
+        ok(lib.L, lib.L.bg_hashjoin_free(tables[k][0]))
+        ok(lib.L, lib.L.bg_hashjoin_free2(tables[k][1]))
     return rec
 
 
@@ -218,7 +245,12 @@ def main():
         ROOT, "profiles", "perf_join_filter.json"))
     ap.add_argument("--scale", type=float, default=1.0,
                     help="shrink both sides (rehearsal only)")
+    ap.add_argument("--parent-lib", help="the parent commit's "
+                    "libballista_gpu.so: every plan and phase also runs on "
+                    "it, alternated with this tree's library")
+    ap.add_argument("--repeats", type=int, default=REPEATS)
     args = ap.parse_args()
+    repeats = args.repeats
     assert torch.cuda.is_available(), "needs the GPU: there is no fallback"
     nb, npr = int(N_BUILD * args.scale), int(N_PROBE * args.scale)
     dev = torch.device("cuda:0")
@@ -241,42 +273,57 @@ def main():
                          ("o_seven", torch.full_like(number, 7))]}
     del number
     torch.cuda.synchronize()
-    lib = Lib(tables)
-    rec = {"build_rows": nb, "probe_rows": npr, "repeats": REPEATS,
+    libs = {"new": Lib(None, tables)}
+    rec = {"build_rows": nb, "probe_rows": npr, "repeats": repeats,
            "timing": "host clock around bg_execute_stage (returns rows, so "
                      "device work is complete); 1 warm-up run per plan; the "
-                     "plans of a pair alternate",
-           "source_hash": lib.hash, "pairs": {}}
+                     "plans of a pair, and the libraries, alternate",
+           "source_hash": libs["new"].hash, "pairs": {}}
+    if args.parent_lib:
+        libs["parent"] = Lib(os.path.abspath(args.parent_lib), tables)
+        rec["parent_source_hash"] = libs["parent"].hash
+        assert libs["parent"].hash != libs["new"].hash
     for pair, docs in PAIRS.items():
-        results = {}
-        for name, d in docs.items():
-            _, results[name] = lib.run(d)               # warm-up
-        times = {name: [] for name in docs}
-        for _ in range(REPEATS):                        # alternated
+        results = {(k, name): lib.run(d)[1] for name, d in docs.items()
+                   for k, lib in libs.items()}          # warm-up
+        times = {key: [] for key in results}
+        for r in range(repeats):                        # alternated
+            # the library that goes first changes every round: whichever
+            # runs a plan second finds the plan's tables in the cache
+            turn = list(libs.items())[::-1 if r % 2 else 1]
             for name, d in docs.items():
-                dt, res = lib.run(d)
-                assert res == results[name]
-                times[name].append(dt)
-        (na, a), (nb_, b) = results.items()
-        assert a == b, f"{pair}: {na} {a} != {nb_} {b}"
-        out = {name: dict(spread(times[name]), sum_custkey=results[name][0],
-                          rows=results[name][1]) for name in docs}
+                for k, lib in turn:
+                    dt, res = lib.run(d)
+                    assert res == results[k, name]
+                    times[k, name].append(dt)
+        assert len({tuple(v) for v in results.values()}) == 1, results
+        by_lib = {k: {name: dict(spread(times[k, name]),
+                                 sum_custkey=results[k, name][0],
+                                 rows=results[k, name][1]) for name in docs}
+                  for k in libs}
+        out = by_lib["new"]
         new, old = (out[n] for n in docs)
         out["first_minus_second_median_s"] = new["median_s"] - old["median_s"]
         out["second_min_max_spread_s"] = old["max_s"] - old["min_s"]
         if pair == "inner_ne":
             out["within_bar"] = (out["first_minus_second_median_s"]
                                  <= out["second_min_max_spread_s"])
+        if "parent" in by_lib:
+            out["parent"] = by_lib["parent"]
         rec["pairs"][pair] = out
-        print(json.dumps({pair: {k: v["median_s"] if isinstance(v, dict)
-                                 else v for k, v in out.items()}}),
-              flush=True)
-    rec["abi_breakdown"] = abi_breakdown(lib.L, c_custkey, c_x, o_custkey,
-                                         o_x)
+        print(json.dumps({pair: {
+            k: {name: v["median_s"] for name, v in by_lib[k].items()
+                if name in docs} for k in libs}}), flush=True)
+    abi = abi_breakdown(libs, repeats, c_custkey, c_x, o_custkey, o_x)
+    rec["abi_breakdown"] = abi["new"]
+    if "parent" in abi:
+        rec["abi_breakdown_parent"] = abi["parent"]
     print(json.dumps({"abi_breakdown": {
-        k: {"pairs": v["pairs"], "count_median_s": v["count"]["median_s"],
-            "fill_median_s": v["fill"]["median_s"]}
-        for k, v in rec["abi_breakdown"].items()}}), flush=True)
+        lib: {k: {"pairs": v["pairs"],
+                  "count_median_s": v["count"]["median_s"],
+                  "fill_median_s": v["fill"]["median_s"]}
+              for k, v in paths.items()} for lib, paths in abi.items()}}),
+          flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(rec, f, indent=1)

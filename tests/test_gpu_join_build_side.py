@@ -219,6 +219,92 @@ def test_count_and_fill_refuse_build_rows_only_types(ctx, join_type):
         j.free()
 
 
+def balanced(ctx, call):
+    """call() leaves the pool's live bytes and buffers as it found them."""
+    gc.collect()
+    before = ctx.pool_stats()[:2]
+    ret = call()
+    assert ctx.pool_stats()[:2] == before
+    return ret
+
+
+# The checks below are made on the host, before anything is allocated or
+# launched: 65 build rows, 130 probe rows, one Int64 key.
+N_BUILD, N_PROBE = 65, 130
+SENTINEL = 0xDEADBEEF
+
+
+@pytest.fixture()
+def small_join(ctx):
+    """-> (handle over the Int64 build key, Int64 probe key column)."""
+    j = Join(ctx, key_col(ctx, np.arange(N_BUILD)), N_BUILD)
+    yield j, key_col(ctx, np.arange(N_PROBE) % (N_BUILD + 7))
+    j.free()
+
+
+def test_fill_refuses_keys_that_differ_from_the_build(ctx, small_join):
+    """An Int32 probe column after an Int64 build would be read with 8-byte
+    elements; a second key column has no build column to compare with."""
+    j, pcol = small_join
+    L = ctx.L
+    m = I64()
+    assert L.bg_hashjoin_probe_count2(j.h, cols(pcol), 1, I64(N_PROBE), INNER,
+                                      ctypes.byref(m)) == BG_OK
+    assert 0 < m.value <= N_PROBE
+    i32col, _ = ctx.upload_column(
+        (np.arange(N_PROBE) % (N_BUILD + 7)).astype(np.int32),
+        gpu.BG_DT_INT32)
+    outs = [ctx.alloc(4 * N_PROBE) for _ in range(2)]
+    for o in outs:
+        o.upload(np.full(N_PROBE, SENTINEL, dtype=np.uint32))
+    for bad, nkeys in ((cols(i32col), 1), (cols(pcol, pcol), 2)):
+        rc = balanced(ctx, lambda: L.bg_hashjoin_probe_fill2(
+            j.h, bad, nkeys, I64(N_PROBE), INNER, outs[0].ptr, outs[1].ptr))
+        assert rc == BG_ERR_INVALID
+        assert L.bg_last_error() != b""
+        # no kernel ran: nothing was written
+        for o in outs:
+            assert np.all(o.download(np.uint32, N_PROBE) == SENTINEL)
+    # the count's offsets are still good for a fill with the right keys
+    assert L.bg_hashjoin_probe_fill2(j.h, cols(pcol), 1, I64(N_PROBE), INNER,
+                                     outs[0].ptr, outs[1].ptr) == BG_OK
+    got = outs[0].download(np.uint32, N_PROBE)
+    assert np.all(got[:m.value] != SENTINEL)
+    assert np.all(got[m.value:] == SENTINEL)
+
+
+@pytest.mark.parametrize("join_type", [8, -1])
+def test_count_refuses_an_unknown_join_type(ctx, small_join, join_type):
+    j, pcol = small_join
+    m = I64(-1)
+    rc = balanced(ctx, lambda: ctx.L.bg_hashjoin_probe_count2(
+        j.h, cols(pcol), 1, I64(N_PROBE), join_type, ctypes.byref(m)))
+    assert rc == BG_ERR_INVALID
+    assert b"join_type" in ctx.L.bg_last_error()
+    assert m.value == -1
+
+
+def test_null_handle_is_refused(ctx, small_join):
+    _, pcol = small_join
+    L, null = ctx.L, ctypes.c_void_p()
+    m, cnt = I64(-1), I64(-1)
+    out = ctx.alloc(4 * N_PROBE)
+    calls = [
+        lambda: L.bg_hashjoin_probe_count2(null, cols(pcol), 1, I64(N_PROBE),
+                                           INNER, ctypes.byref(m)),
+        lambda: L.bg_hashjoin_probe_fill2(null, cols(pcol), 1, I64(N_PROBE),
+                                          INNER, out.ptr, out.ptr),
+        lambda: L.bg_hashjoin_probe_mark2(null, cols(pcol), 1, I64(N_PROBE)),
+        lambda: L.bg_hashjoin_build_rows2(null, 1, ctypes.byref(cnt),
+                                          out.ptr),
+    ]
+    for call in calls:
+        assert balanced(ctx, call) == BG_ERR_INVALID
+        assert b"null join handle" in L.bg_last_error()
+    assert m.value == -1 and cnt.value == -1
+    assert L.bg_hashjoin_free2(null) == BG_OK
+
+
 def test_pool_balance(ctx):
     """Only the bitmap may stay live: the first marking call adds exactly
     one buffer, a second one and build_rows2 add nothing, and free2 gives
@@ -230,13 +316,6 @@ def test_pool_balance(ctx):
     cnt = I64()
     L = ctx.L
 
-    def balanced(call):
-        gc.collect()
-        before = ctx.pool_stats()[:2]
-        ret = call()
-        assert ctx.pool_stats()[:2] == before
-        return ret
-
     gc.collect()
     base = ctx.pool_stats()[:2]
     h = ctypes.c_void_p()
@@ -245,17 +324,17 @@ def test_pool_balance(ctx):
     built = ctx.pool_stats()[:2]
     assert built[1] == base[1] + 2                 # nodes + head, no bitmap
     # valid before any marking call, and allocates nothing
-    assert balanced(lambda: L.bg_hashjoin_build_rows2(
+    assert balanced(ctx, lambda: L.bg_hashjoin_build_rows2(
         h, 0, ctypes.byref(cnt), out.ptr)) == BG_OK and cnt.value == n
     assert L.bg_hashjoin_probe_mark2(h, cols(pcol), 1, I64(n)) == BG_OK
     assert ctx.pool_stats()[1] == built[1] + 1     # + the bitmap
-    assert balanced(lambda: L.bg_hashjoin_probe_mark2(
+    assert balanced(ctx, lambda: L.bg_hashjoin_probe_mark2(
         h, cols(pcol), 1, I64(n))) == BG_OK
     for matched in (1, 0):
-        assert balanced(lambda: L.bg_hashjoin_build_rows2(
+        assert balanced(ctx, lambda: L.bg_hashjoin_build_rows2(
             h, matched, ctypes.byref(cnt), out.ptr)) == BG_OK
         assert cnt.value == n // 2
-        assert balanced(lambda: L.bg_hashjoin_build_rows2(
+        assert balanced(ctx, lambda: L.bg_hashjoin_build_rows2(
             h, matched, ctypes.byref(cnt), None)) == BG_OK
     assert L.bg_hashjoin_free2(h) == BG_OK
     gc.collect()
