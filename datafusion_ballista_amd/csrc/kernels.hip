@@ -8288,3 +8288,477 @@ extern "C" int bg_project_dec128_multi(
   if (rc != BG_OK) return set_err(BG_ERR_HIP, "k_project_multi launch");
   return BG_OK;
 }
+
+// ---------------------------------------------------------------------------
+// CAST, Float64 arithmetic and Decimal128 division (approved/q8.txt:103,
+// q11.txt:70,74, q14.txt:22, q17.txt:19,27,33, q20.txt:49, q22.txt:18).
+// Elementwise, one row per lane.  A conversion that can fail on a row
+// (DataFusion casts with safe=false, decimal div raises DivideByZero) runs
+// through k_rows_checked: whole waves walk 64-row words, NULL rows are
+// never examined, failing VALID rows are counted by ballot + popcount and
+// each wave that saw one adds its count with a single atomic.  A
+// conversion that cannot fail runs through k_rows: no counter, no read
+// back.
+// ---------------------------------------------------------------------------
+
+// One 64-row word of an Arrow validity bitmap of which only ceil(n/8) bytes
+// are known to exist: an 8-byte load where the whole word lies inside them
+// and the bitmap is 8-byte aligned, the remaining bytes one by one else.
+__device__ __forceinline__ u64 valid_word(const uint8_t* bm, int64_t w,
+                                          int64_t n) {
+  const int64_t nbytes = (n + 7) >> 3, off = w << 3;
+  if (((uintptr_t)bm & 7u) == 0 && off + 8 <= nbytes)
+    return *reinterpret_cast<const u64*>(bm + off);
+  u64 v = 0;
+  for (int k = 0; k < 8 && off + k < nbytes; ++k)
+    v |= (u64)bm[off + k] << (8 * k);
+  return v;
+}
+
+__device__ __forceinline__ void store_dec128(void* base, int64_t row, i128 v) {
+  ulong2 o;
+  o.x = (u64)(u128)v;
+  o.y = (u64)((u128)v >> 64);
+  reinterpret_cast<ulong2*>(base)[row] = o;
+}
+
+__device__ __forceinline__ u128 abs_u128(i128 x) {
+  return x < 0 ? (u128)0 - (u128)x : (u128)x;
+}
+
+__device__ __forceinline__ i128 signed_i128(u128 mag, bool neg) {
+  return (i128)(neg ? (u128)0 - mag : mag);
+}
+
+// (double)x of an i128, rounded once to nearest-even: the magnitude's top
+// 64 bits with every dropped bit folded into bit 0 (far below the round
+// bit at bit 10) convert with the single rounding of u64 -> f64, and the
+// power-of-two scale is exact.
+__device__ __forceinline__ double i128_to_f64(i128 x) {
+  const u128 u = abs_u128(x);
+  const u64 hi = (u64)(u >> 64), lo = (u64)u;
+  double r;
+  if (hi == 0) {
+    r = (double)lo;
+  } else {
+    const int lz = __clzll((long long)hi);
+    const u64 top = lz ? (hi << lz) | (lo >> (64 - lz)) : hi;
+    const u64 dropped = lz ? lo << lz : lo;
+    r = ldexp((double)(top | (u64)(dropped != 0)), 64 - lz);
+  }
+  return x < 0 ? -r : r;
+}
+
+// an INTEGRAL double of magnitude below 2^127 as i128, exactly
+__device__ __forceinline__ i128 f64_integral_to_i128(double r) {
+  const u64 bits = (u64)__double_as_longlong(r);
+  const int e = (int)((bits >> 52) & 0x7FF);
+  if (e < 1023) return 0;  // |r| < 1
+  const u64 m = (bits & 0xFFFFFFFFFFFFFull) | (1ull << 52);
+  const int sh = e - 1075;  // |r| = m * 2^sh, sh <= 74
+  const u128 u = sh >= 0 ? (u128)m << sh : (u128)(m >> -sh);
+  return signed_i128(u, (bits >> 63) != 0);
+}
+
+// Each row functor's run(row) loads, converts, stores and returns 0, or
+// the 1-based kind of failure the row met.
+template <typename Op>
+__global__ __launch_bounds__(BG_BLOCK) void k_rows(Op op, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    (void)op.run(i);
+}
+
+// failed[k-1] += number of valid rows whose run() returned k (1..KINDS)
+template <int KINDS, typename Op>
+__global__ __launch_bounds__(BG_BLOCK) void k_rows_checked(
+    Op op, const uint8_t* __restrict__ avalid,
+    const uint8_t* __restrict__ bvalid, int64_t n, u64* failed) {
+  const int lane = lane_id();
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  u64 nfail[KINDS] = {};
+  // the wave's first row: a multiple of 64, so one bitmap word per step
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x + threadIdx.x - lane;
+       base < n; base += stride) {
+    u64 live = ~0ull;
+    if (avalid) live &= valid_word(avalid, base >> 6, n);
+    if (bvalid) live &= valid_word(bvalid, base >> 6, n);
+    const int64_t row = base + lane;
+    int fail = 0;
+    if (row < n && ((live >> lane) & 1)) fail = op.run(row);
+#pragma unroll
+    for (int k = 0; k < KINDS; ++k)
+      nfail[k] += (u64)__popcll(__ballot(fail == k + 1));
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < KINDS; ++k)
+      if (nfail[k]) atomicAdd(&failed[k], nfail[k]);
+  }
+}
+
+template <typename S>
+__device__ __forceinline__ i128 load_as_i128(const void* base, int64_t row) {
+  if constexpr (sizeof(S) == 16)
+    return load_dec128(base, row);
+  else
+    return (i128) reinterpret_cast<const S*>(base)[row];
+}
+
+// Int32 / Int64 -> Float64: (double)x.  Decimal128(p,s) -> Float64:
+// (double)x / 1e<s>, two correctly rounded operations.
+template <typename S>
+struct OpCastToF64 {
+  const void* in;
+  double p10;
+  double* out;
+  __device__ __forceinline__ int run(int64_t i) const {
+    if constexpr (sizeof(S) == 16)
+      out[i] = i128_to_f64(load_dec128(in, i)) / p10;
+    else
+      out[i] = (double)reinterpret_cast<const S*>(in)[i];
+    return 0;
+  }
+};
+
+struct OpCastI32ToI64 {
+  const int32_t* in;
+  int64_t* out;
+  __device__ __forceinline__ int run(int64_t i) const {
+    out[i] = (int64_t)in[i];
+    return 0;
+  }
+};
+
+// x * 10^k into Decimal128(p,s); fails where |x| >= bound = 10^(p-k), which
+// is |x * 10^k| >= 10^p without a multiply that could wrap
+template <typename S>
+struct OpCastScaleUp {
+  const void* in;
+  i128 mul;
+  u128 bound;
+  void* out;
+  __device__ __forceinline__ int run(int64_t i) const {
+    const i128 x = load_as_i128<S>(in, i);
+    store_dec128(out, i, (i128)((u128)x * (u128)mul));
+    return abs_u128(x) >= bound ? 1 : 0;
+  }
+};
+
+// x / 10^k rounded half away from zero; fails where |result| >= 10^p
+struct OpCastScaleDown {
+  const void* in;
+  u128 div, limit;
+  void* out;
+  __device__ __forceinline__ int run(int64_t i) const {
+    const i128 x = load_dec128(in, i);
+    const u128 u = abs_u128(x);
+    u128 q = u / div;
+    const u128 r = u - q * div;
+    if (2 * r >= div) q += 1;  // r < div <= 10^38: 2 * r cannot wrap
+    store_dec128(out, i, signed_i128(q, x < 0));
+    return q >= limit ? 1 : 0;
+  }
+};
+
+// round(v * 1e<s>), C round(); fails on NaN, +-inf and |r| >= 10^p
+struct OpCastF64ToDec {
+  const double* in;
+  double p10;
+  u128 limit;
+  void* out;
+  __device__ __forceinline__ int run(int64_t i) const {
+    const double r = round(in[i] * p10);
+    // NaN compares false; 2^127 bounds what f64_integral_to_i128 takes
+    bool ok = fabs(r) < 1.7014118346046923e38;
+    const i128 q = ok ? f64_integral_to_i128(r) : (i128)0;
+    ok = ok && abs_u128(q) < limit;
+    store_dec128(out, i, ok ? q : (i128)0);
+    return ok ? 0 : 1;
+  }
+};
+
+// arrow-rs decimal div after scale alignment: (a * 10^m) / b for UP, else
+// a / (b * 10^m), truncated toward zero.  Kind 1: b == 0.  Kind 2: the
+// scaled operand leaves i128 (|operand| > fit = (2^127 - 1) / 10^m).
+template <bool UP>
+struct OpDivDec128 {
+  const void* a;
+  const void* b;
+  u128 p10, fit;
+  void* out;
+  __device__ __forceinline__ int run(int64_t i) const {
+    const i128 x = load_dec128(a, i), y = load_dec128(b, i);
+    u128 ux = abs_u128(x), uy = abs_u128(y);
+    int fail = 0;
+    if (uy == 0) fail = 1;
+    else if ((UP ? ux : uy) > fit) fail = 2;
+    u128 q = 0;
+    if (!fail) {
+      if (UP) ux *= p10; else uy *= p10;
+      q = ux / uy;
+    }
+    store_dec128(out, i, signed_i128(q, (x < 0) != (y < 0)));
+    return fail;
+  }
+};
+
+template <typename Op>
+static int launch_rows(Op op, int64_t n) {
+  hipLaunchKernelGGL(k_rows<Op>, dim3(grid_for(n)), dim3(BG_BLOCK), 0, 0, op,
+                     n);
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+// launch the counting form and read the KINDS counters back
+template <int KINDS, typename Op>
+static int launch_rows_checked(Op op, const uint8_t* avalid,
+                               const uint8_t* bvalid, int64_t n,
+                               u64* h_failed) {
+  DevBuf<u64> d_failed;
+  HIP_TRY(d_failed.alloc(KINDS));
+  HIP_TRY(hipMemsetAsync(d_failed, 0, sizeof(u64) * KINDS, 0));
+  hipLaunchKernelGGL((k_rows_checked<KINDS, Op>), dim3(grid_for(n)),
+                     dim3(BG_BLOCK), 0, 0, op, avalid, bvalid, n,
+                     d_failed.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(h_failed, d_failed, sizeof(u64) * KINDS,
+                    hipMemcpyDeviceToHost));
+  return BG_OK;
+}
+
+// the correctly rounded doubles 1e0..1e38
+static const double BG_P10_F64[39] = {
+    1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,
+    1e10, 1e11, 1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19,
+    1e20, 1e21, 1e22, 1e23, 1e24, 1e25, 1e26, 1e27, 1e28, 1e29,
+    1e30, 1e31, 1e32, 1e33, 1e34, 1e35, 1e36, 1e37, 1e38};
+
+static u128 p10_u128(int k) {  // k in [0, 38]
+  u128 r = 1;
+  while (k-- > 0) r *= 10;
+  return r;
+}
+
+static bool dec_spec_ok(int32_t precision, int32_t scale) {
+  return precision >= 1 && precision <= 38 && scale >= 0 && scale <= precision;
+}
+
+extern "C" int bg_cast(const bg_column* src, int32_t to_dtype,
+                       int32_t to_precision, int32_t to_scale, int64_t n,
+                       void* d_out, int64_t* out_failed) {
+  REQUIRE_INIT();
+  if (out_failed) *out_failed = 0;
+  if (!src || n < 0)
+    return set_err(BG_ERR_INVALID, "bg_cast: NULL column or negative n");
+  const int32_t from = src->dtype;
+  const bool from_int = from == BG_DT_INT32 || from == BG_DT_INT64;
+  const bool from_dec = from == BG_DT_DECIMAL128;
+  const bool ok_pair =
+      (to_dtype == BG_DT_FLOAT64 && (from_int || from_dec)) ||
+      (to_dtype == BG_DT_DECIMAL128 &&
+       (from_int || from_dec || from == BG_DT_FLOAT64)) ||
+      (to_dtype == BG_DT_INT64 && from == BG_DT_INT32);
+  if (!ok_pair) {
+    char msg[128];
+    snprintf(msg, sizeof(msg), "bg_cast: dtype %d to dtype %d unsupported",
+             (int)from, (int)to_dtype);
+    return set_err(BG_ERR_UNSUPPORTED, msg);
+  }
+  if (from_dec && (src->scale < 0 || src->scale > 38))
+    return set_err(BG_ERR_INVALID, "bg_cast: source scale outside 0..38");
+  if (to_dtype == BG_DT_DECIMAL128 && !dec_spec_ok(to_precision, to_scale))
+    return set_err(BG_ERR_INVALID,
+                   "bg_cast: Decimal128 target needs 1 <= precision <= 38 "
+                   "and 0 <= scale <= precision");
+  if (n == 0) return BG_OK;
+
+  if (to_dtype == BG_DT_FLOAT64) {
+    double* out = (double*)d_out;
+    if (from == BG_DT_INT32)
+      return launch_rows(OpCastToF64<int32_t>{src->d_data, 1.0, out}, n);
+    if (from == BG_DT_INT64)
+      return launch_rows(OpCastToF64<int64_t>{src->d_data, 1.0, out}, n);
+    return launch_rows(
+        OpCastToF64<i128>{src->d_data, BG_P10_F64[src->scale], out}, n);
+  }
+  if (to_dtype == BG_DT_INT64)
+    return launch_rows(
+        OpCastI32ToI64{(const int32_t*)src->d_data, (int64_t*)d_out}, n);
+
+  // -> Decimal128(to_precision, to_scale).  in_digits bounds the source's
+  // decimal digits (0: unknown); a conversion whose widest input still
+  // fits the target runs unchecked.
+  const uint8_t* valid = src->d_validity;
+  u64 failed = 0;
+  int rc;
+  if (from == BG_DT_FLOAT64) {
+    rc = launch_rows_checked<1>(
+        OpCastF64ToDec{(const double*)src->d_data, BG_P10_F64[to_scale],
+                       p10_u128(to_precision), d_out},
+        valid, nullptr, n, &failed);
+  } else {
+    const int in_digits = from == BG_DT_INT32   ? 10
+                          : from == BG_DT_INT64 ? 19
+                          : (src->precision >= 1 && src->precision <= 38)
+                              ? src->precision : 0;
+    const int shift = to_scale - (from_dec ? src->scale : 0);
+    if (shift >= 0) {
+      const bool fits = in_digits > 0 && in_digits + shift <= to_precision;
+      const i128 mul = (i128)p10_u128(shift);
+      const u128 bound =
+          shift <= to_precision ? p10_u128(to_precision - shift) : (u128)1;
+#define BG_CAST_UP(S)                                                       \
+  (fits ? launch_rows(OpCastScaleUp<S>{src->d_data, mul, bound, d_out}, n)  \
+        : launch_rows_checked<1>(                                           \
+              OpCastScaleUp<S>{src->d_data, mul, bound, d_out}, valid,      \
+              nullptr, n, &failed))
+      rc = from == BG_DT_INT32   ? BG_CAST_UP(int32_t)
+           : from == BG_DT_INT64 ? BG_CAST_UP(int64_t)
+                                 : BG_CAST_UP(i128);
+#undef BG_CAST_UP
+    } else {
+      // rounding can carry into one more digit: 99.5 -> 100
+      const bool fits = in_digits > 0 && in_digits + shift < to_precision;
+      const OpCastScaleDown op{src->d_data, p10_u128(-shift),
+                               p10_u128(to_precision), d_out};
+      rc = fits ? launch_rows(op, n)
+                : launch_rows_checked<1>(op, valid, nullptr, n, &failed);
+    }
+  }
+  if (rc != BG_OK) return rc;
+  if (out_failed) *out_failed = (int64_t)failed;
+  if (failed) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "cast: %llu of %lld rows %s Decimal128(%d,%d)",
+             failed, (long long)n,
+             from == BG_DT_FLOAT64 ? "are NaN, infinite or overflow"
+                                   : "overflow",
+             (int)to_precision, (int)to_scale);
+    return set_err(BG_ERR_INVALID, msg);
+  }
+  return BG_OK;
+}
+
+// Float64 arithmetic, exactly one IEEE-754 binary64 operation per row (no
+// fast-math in the build, and no multiply feeds an add here, so
+// -ffp-contract has nothing to fuse).  Two rows per lane through 16-byte
+// accesses (nvec of them) when every pointer is 16-byte aligned, scalar
+// loop for the rest.
+template <int OP>
+__device__ __forceinline__ double f64_op(double a, double b) {
+  switch (OP) {
+    case BG_F64_MUL: case BG_F64_MUL_LIT: return a * b;
+    case BG_F64_ADD: case BG_F64_ADD_LIT: return a + b;
+    case BG_F64_SUB: return a - b;
+    case BG_F64_DIV: case BG_F64_DIV_LIT: return a / b;
+    case BG_F64_LIT_SUB: return b - a;
+    default: return b / a;  // BG_F64_LIT_DIV
+  }
+}
+
+template <int OP>
+__global__ __launch_bounds__(BG_BLOCK) void k_project_f64(
+    const double* __restrict__ a, const double* __restrict__ b, double lit,
+    int64_t n, int64_t nvec, double* __restrict__ out) {
+  typedef double f64x2_pj __attribute__((ext_vector_type(2)));
+  constexpr bool BINARY = OP <= BG_F64_DIV;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t v = tid; v < nvec; v += stride) {
+    const f64x2_pj x = reinterpret_cast<const f64x2_pj*>(a)[v];
+    f64x2_pj y = {lit, lit};
+    if (BINARY) y = reinterpret_cast<const f64x2_pj*>(b)[v];
+    f64x2_pj r;
+    r[0] = f64_op<OP>(x[0], y[0]);
+    r[1] = f64_op<OP>(x[1], y[1]);
+    reinterpret_cast<f64x2_pj*>(out)[v] = r;
+  }
+  for (int64_t i = nvec * 2 + tid; i < n; i += stride)
+    out[i] = f64_op<OP>(a[i], BINARY ? b[i] : lit);
+}
+
+template <int OP>
+static void launch_project_f64(const double* a, const double* b, double lit,
+                               int64_t n, double* out) {
+  const bool aligned =
+      (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15u) == 0;
+  const int64_t nvec = aligned ? n / 2 : 0;
+  hipLaunchKernelGGL(k_project_f64<OP>, dim3(grid_for(nvec > 0 ? nvec : n)),
+                     dim3(BG_BLOCK), 0, 0, a, b, lit, n, nvec, out);
+}
+
+extern "C" int bg_project_f64(int32_t op, const bg_column* a,
+                              const bg_column* b, double lit, int64_t n,
+                              double* d_out) {
+  REQUIRE_INIT();
+  if (op < BG_F64_MUL || op > BG_F64_LIT_DIV)
+    return set_err(BG_ERR_INVALID, "bg_project_f64: unknown op");
+  const bool binary = op <= BG_F64_DIV;
+  if (!a || (binary && !b))
+    return set_err(BG_ERR_INVALID, "bg_project_f64: missing column operand");
+  if (a->dtype != BG_DT_FLOAT64 || (binary && b->dtype != BG_DT_FLOAT64))
+    return set_err(BG_ERR_INVALID, "bg_project_f64: Float64 columns required");
+  if (n < 0) return set_err(BG_ERR_INVALID, "bg_project_f64: negative n");
+  if (n == 0) return BG_OK;
+  const double* pa = (const double*)a->d_data;
+  const double* pb = binary ? (const double*)b->d_data : nullptr;
+  switch (op) {
+#define BG_F64_CASE(OP) \
+  case OP: launch_project_f64<OP>(pa, pb, lit, n, d_out); break
+    BG_F64_CASE(BG_F64_MUL);
+    BG_F64_CASE(BG_F64_ADD);
+    BG_F64_CASE(BG_F64_SUB);
+    BG_F64_CASE(BG_F64_DIV);
+    BG_F64_CASE(BG_F64_MUL_LIT);
+    BG_F64_CASE(BG_F64_ADD_LIT);
+    BG_F64_CASE(BG_F64_LIT_SUB);
+    BG_F64_CASE(BG_F64_DIV_LIT);
+    BG_F64_CASE(BG_F64_LIT_DIV);
+#undef BG_F64_CASE
+  }
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+extern "C" int bg_div_dec128(const bg_column* a, const bg_column* b,
+                             int32_t mul_pow, int64_t n, void* d_out,
+                             int64_t* out_failed) {
+  REQUIRE_INIT();
+  if (out_failed) *out_failed = 0;
+  if (!a || !b || n < 0)
+    return set_err(BG_ERR_INVALID, "bg_div_dec128: NULL column or negative n");
+  if (a->dtype != BG_DT_DECIMAL128 || b->dtype != BG_DT_DECIMAL128)
+    return set_err(BG_ERR_INVALID, "bg_div_dec128: Decimal128 columns required");
+  if (mul_pow < -38 || mul_pow > 38)
+    return set_err(BG_ERR_INVALID, "bg_div_dec128: mul_pow outside -38..38");
+  if (n == 0) return BG_OK;
+  const u128 p10 = p10_u128(mul_pow < 0 ? -mul_pow : mul_pow);
+  const u128 fit = (((u128)1 << 127) - 1) / p10;
+  u64 failed[2] = {0, 0};
+  const int rc =
+      mul_pow >= 0
+          ? launch_rows_checked<2>(
+                OpDivDec128<true>{a->d_data, b->d_data, p10, fit, d_out},
+                a->d_validity, b->d_validity, n, failed)
+          : launch_rows_checked<2>(
+                OpDivDec128<false>{a->d_data, b->d_data, p10, fit, d_out},
+                a->d_validity, b->d_validity, n, failed);
+  if (rc != BG_OK) return rc;
+  if (out_failed) *out_failed = (int64_t)(failed[0] + failed[1]);
+  if (failed[0] || failed[1]) {
+    char zero[64] = "", wide[80] = "";
+    if (failed[0])
+      snprintf(zero, sizeof(zero), "division by zero in %llu row%s", failed[0],
+               failed[0] == 1 ? "" : "s");
+    if (failed[1])
+      snprintf(wide, sizeof(wide), "scaled operand overflows i128 in %llu row%s",
+               failed[1], failed[1] == 1 ? "" : "s");
+    char msg[192];
+    snprintf(msg, sizeof(msg), "div: %s%s%s", zero,
+             failed[0] && failed[1] ? ", " : "", wide);
+    return set_err(BG_ERR_INVALID, msg);
+  }
+  return BG_OK;
+}

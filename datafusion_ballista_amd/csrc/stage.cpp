@@ -1025,10 +1025,149 @@ static DBufPtr eval_filter_mask(const Table& t, const Value& node);
 struct ExprVal {
   bool is_lit = false;
   Col col;          // when !is_lit (shares buffers)
-  int64_t lit_lo = 0, lit_hi = 0;  // when is_lit (i128)
+  int64_t lit_lo = 0, lit_hi = 0;  // when is_lit (i128; lit_f64: its bits)
+  bool is_f64 = false;             // a lit_f64 literal
+  double f64 = 0.0;
 };
 
 static ExprVal eval_expr(const Table& t, const Value& e);
+static std::string expr_label(const Value& e);
+
+// ---- cast / div / Float64 arithmetic: the verdicts that validate_expr and
+// eval_expr both read, so what validation accepts is what execution runs ----
+
+static const DtSpec DT_LIT{BG_DT_DECIMAL128, 38, 0};
+static const DtSpec DT_F64{BG_DT_FLOAT64, 0, 0};
+
+static bool is_literal_node(const Value& e) {
+  return e.has("lit") || e.has("lit_f64");
+}
+
+// {"lit_f64": <JSON number>}; an integer token converts
+static double lit_f64_value(const Value& e) {
+  const Value& v = e.at("lit_f64");
+  if (v.kind == Value::DBL) return v.d;
+  if (v.kind == Value::INT) return (double)v.i;
+  throw StageError(BG_ERR_INVALID, "lit_f64: value must be a JSON number");
+}
+
+static std::string spec_name(const DtSpec& d) {
+  std::string s = dtype_name(d.dt);
+  if (d.dt == BG_DT_DECIMAL128)
+    s += "(" + std::to_string(d.precision) + "," + std::to_string(d.scale) +
+         ")";
+  return s;
+}
+
+// {"cast": {"arg": expr, "to": {"dtype", "precision"?, "scale"?}}}: the
+// target type, decimal128 with both of its parameters spelled out
+static DtSpec cast_target(const Value& c) {
+  const Value& to = c.at("to");
+  if (to.get_str("dtype") != "decimal128") return parse_dtype(to);
+  const std::string arg = expr_label(c.at("arg"));
+  for (const char* k : {"precision", "scale"})
+    if (!to.has(k) || to.at(k).kind != Value::INT)
+      throw StageError(BG_ERR_INVALID,
+                       "cast: decimal128 target of '" + arg +
+                           "' requires an integer '" + k + "'");
+  const DtSpec d{BG_DT_DECIMAL128, (int32_t)to.get_int("precision"),
+                 (int32_t)to.get_int("scale")};
+  if (to.get_int("precision") < 1 || to.get_int("precision") > 38 ||
+      to.get_int("scale") < 0 || to.get_int("scale") > to.get_int("precision"))
+    throw StageError(BG_ERR_INVALID,
+                     "cast: illegal target " + spec_name(d) + " of '" + arg +
+                         "': 1 <= precision <= 38 and 0 <= scale <= "
+                         "precision required");
+  return d;
+}
+
+// the pairs bg_cast converts
+static void cast_check_pair(const Value& c, const DtSpec& from,
+                            const DtSpec& to) {
+  const std::string arg = expr_label(c.at("arg"));
+  if (is_literal_node(c.at("arg")))
+    throw StageError(BG_ERR_INVALID, "cast: argument '" + arg +
+                                         "' is a literal; cast a column");
+  const bool from_int = from.dt == BG_DT_INT32 || from.dt == BG_DT_INT64;
+  const bool from_dec = from.dt == BG_DT_DECIMAL128;
+  const bool ok =
+      (to.dt == BG_DT_FLOAT64 && (from_int || from_dec)) ||
+      (to.dt == BG_DT_DECIMAL128 &&
+       (from_int || from_dec || from.dt == BG_DT_FLOAT64)) ||
+      (to.dt == BG_DT_INT64 && from.dt == BG_DT_INT32);
+  if (!ok)
+    throw StageError(BG_ERR_UNSUPPORTED,
+                     "cast: '" + arg + "' (" + spec_name(from) + ") to " +
+                         spec_name(to) + " is not supported");
+}
+
+// What mul|add|sub|div over operands of types a and b (a literal node's
+// type is its literal kind's) runs as.
+struct ArithPlan {
+  enum Kind { DEC128, F64, DEC_DIV } kind = DEC128;
+  int32_t f64_op = 0;       // F64: BG_F64_*
+  bool negate_lit = false;  // F64: col - lit runs as col + (-lit), the same
+                            // IEEE operation
+  DtSpec out{BG_DT_DECIMAL128, 38, 0};  // F64, DEC_DIV
+  int32_t mul_pow = 0;                  // DEC_DIV
+};
+
+static ArithPlan arith_plan(const std::string& k, const Value& e,
+                            const Value& l, const DtSpec& a, const Value& r,
+                            const DtSpec& b) {
+  const bool la = is_literal_node(l), lb = is_literal_node(r);
+  const std::string an = expr_label(l), bn = expr_label(r);
+  const std::string both = "'" + an + "' (" + dtype_name(a.dt) + ") and '" +
+                           bn + "' (" + dtype_name(b.dt) + ")";
+  if (la && lb)
+    throw StageError(BG_ERR_INVALID, k + ": two literals, " + both);
+  ArithPlan p;
+  const bool fa = a.dt == BG_DT_FLOAT64, fb = b.dt == BG_DT_FLOAT64;
+  if (fa || fb) {
+    if (!(fa && fb))
+      throw StageError(BG_ERR_INVALID,
+                       k + ": Float64 operand mixed with another type: " +
+                           both + "; cast one side");
+    p.kind = ArithPlan::F64;
+    p.out = DT_F64;
+    const bool lit = la || lb;
+    if (k == "mul") p.f64_op = lit ? BG_F64_MUL_LIT : BG_F64_MUL;
+    else if (k == "add") p.f64_op = lit ? BG_F64_ADD_LIT : BG_F64_ADD;
+    else if (k == "sub") {
+      p.f64_op = la ? BG_F64_LIT_SUB : lb ? BG_F64_ADD_LIT : BG_F64_SUB;
+      p.negate_lit = lb;
+    } else {
+      p.f64_op = la ? BG_F64_LIT_DIV : lb ? BG_F64_DIV_LIT : BG_F64_DIV;
+    }
+    return p;
+  }
+  if (k != "div") return p;  // the Decimal128 mul|add|sub paths
+  if (la || lb)
+    throw StageError(BG_ERR_UNSUPPORTED,
+                     "div: Decimal128 division takes two columns, '" +
+                         (la ? an : bn) + "' is a literal (" + both + ")");
+  if (a.dt != BG_DT_DECIMAL128 || b.dt != BG_DT_DECIMAL128)
+    throw StageError(BG_ERR_INVALID,
+                     "div: operands must both be decimal128 or both "
+                     "float64: " + both);
+  const int64_t s = e.has("scale") ? e.get_int("scale")
+                                   : std::min<int64_t>(a.scale + 4, 38);
+  const int64_t mul_pow = s - a.scale + b.scale;
+  if (s < 0 || s > 38 || mul_pow < -38 || mul_pow > 38)
+    throw StageError(BG_ERR_INVALID,
+                     "div: result scale " + std::to_string(s) + " for " +
+                         both + ", scales " + std::to_string(a.scale) +
+                         " and " + std::to_string(b.scale) +
+                         ", is outside what Decimal128 can align");
+  p.kind = ArithPlan::DEC_DIV;
+  p.out = {BG_DT_DECIMAL128, 38, (int32_t)s};
+  p.mul_pow = (int32_t)mul_pow;
+  return p;
+}
+
+static DtSpec expr_spec(const ExprVal& v) {
+  return !v.is_lit ? v.col.spec() : v.is_f64 ? DT_F64 : DT_LIT;
+}
 
 // date_part's "part" names (validation and execution both read this)
 static int32_t date_part_code(const std::string& s) {
@@ -1048,10 +1187,50 @@ static void share_validity(const Col& arg, Col* out) {
   out->ext_valid = arg.validity ? nullptr : arg.ext_valid;
 }
 
+// a binary result is NULL where either input is: share the one nullable
+// input's bitmap, AND two
+static void binary_validity(const Table& t, const ExprVal& a,
+                            const ExprVal& b, Col* out) {
+  const Col* ca = !a.is_lit && a.col.nullable() ? &a.col : nullptr;
+  const Col* cb = !b.is_lit && b.col.nullable() ? &b.col : nullptr;
+  if (ca && cb) {
+    out->validity = alloc_bitmap(t.n, 0);
+    chk(bg_bitmap_and(ca->vptr(), cb->vptr(), t.n, out->validity->u8()),
+        "bg_bitmap_and");
+  } else if (ca || cb) {
+    share_validity(ca ? *ca : *cb, out);
+  }
+}
+
+static Col eval_f64_binary(const Table& t, const ArithPlan& p,
+                           const ExprVal& a, const ExprVal& b) {
+  Col out = make_col(p.out);
+  out.data = dalloc_elems(t.n, 8);
+  const ExprVal& first = a.is_lit ? b : a;  // the (first) column operand
+  double lit = a.is_lit ? a.f64 : b.is_lit ? b.f64 : 0.0;
+  if (p.negate_lit) lit = -lit;
+  bg_column ba = to_bg(first.col, t.n), bb = to_bg(b.col, t.n);
+  chk(bg_project_f64(p.f64_op, &ba, (a.is_lit || b.is_lit) ? nullptr : &bb,
+                     lit, t.n, (double*)out.data->p),
+      "bg_project_f64");
+  binary_validity(t, a, b, &out);
+  return out;
+}
+
+static Col eval_dec_div(const Table& t, const ArithPlan& p, const ExprVal& a,
+                        const ExprVal& b) {
+  Col out = make_col(p.out);
+  out.data = dalloc_elems(t.n, 16);
+  bg_column ba = to_bg(a.col, t.n), bb = to_bg(b.col, t.n);
+  // the kernel examines a row only where both inputs are valid
+  chk(bg_div_dec128(&ba, &bb, p.mul_pow, t.n, out.data->p, nullptr),
+      "bg_div_dec128");
+  binary_validity(t, a, b, &out);
+  return out;
+}
+
 static Col eval_dec_binary(const Table& t, int op_cc, int op_cl, int op_lc,
-                           const Value& l, const Value& r) {
-  ExprVal a = eval_expr(t, l);
-  ExprVal b = eval_expr(t, r);
+                           const ExprVal& a, const ExprVal& b) {
   Col out = make_col({BG_DT_DECIMAL128, 38, 0});
   out.data = dalloc_elems(t.n, 16);
   if (!a.is_lit && !b.is_lit) {
@@ -1098,6 +1277,38 @@ static Col eval_dec_binary(const Table& t, int op_cc, int op_cl, int op_lc,
   return out;
 }
 
+// mul|add|sub|div.  Decimal128 arithmetic goes to bg_project_dec128 (op
+// table: 0 a*b, 1 a+b, 2 a-b, 3 lit-a, 4 a*lit, 5 a+lit), Float64 to
+// bg_project_f64, Decimal128 division to bg_div_dec128.
+static Col eval_arith(const Table& t, const std::string& k, const Value& e) {
+  auto& ops = e.get_arr(k);
+  if (ops.size() != 2)
+    throw StageError(BG_ERR_INVALID, k + ": two operands required");
+  ExprVal a = eval_expr(t, *ops[0]);
+  ExprVal b = eval_expr(t, *ops[1]);
+  const ArithPlan p =
+      arith_plan(k, e, *ops[0], expr_spec(a), *ops[1], expr_spec(b));
+  if (p.kind == ArithPlan::F64) return eval_f64_binary(t, p, a, b);
+  if (p.kind == ArithPlan::DEC_DIV) return eval_dec_div(t, p, a, b);
+  if (k == "mul") return eval_dec_binary(t, 0, 4, 4, a, b);
+  if (k == "add") return eval_dec_binary(t, 1, 5, 5, a, b);
+  if (b.is_lit) {
+    // col - lit == col + (-lit): negate the literal side
+    __int128 litv = ((__int128)b.lit_hi << 64) | (uint64_t)b.lit_lo;
+    litv = -litv;
+    Col out = make_col({BG_DT_DECIMAL128, 38, a.col.scale});
+    out.data = dalloc_elems(t.n, 16);
+    bg_column ba = to_bg(a.col, t.n);
+    chk(bg_project_dec128(5, &ba, nullptr, (int64_t)(uint64_t)litv,
+                          (int64_t)(uint64_t)((unsigned __int128)litv >> 64),
+                          t.n, out.data->p),
+        "bg_project_dec128");
+    if (a.col.nullable()) out.validity = a.col.validity;
+    return out;
+  }
+  return eval_dec_binary(t, 2, -1, 3, a, b);
+}
+
 static ExprVal eval_expr(const Table& t, const Value& e) {
   ExprVal v;
   if (e.has("col")) {
@@ -1109,43 +1320,32 @@ static ExprVal eval_expr(const Table& t, const Value& e) {
     parse_i128(e.at("lit"), &v.lit_lo, &v.lit_hi);
     return v;
   }
-  // Decimal128 arithmetic (bg_project_dec128 op table:
-  // 0 a*b, 1 a+b, 2 a-b, 3 lit-a, 4 a*lit, 5 a+lit)
-  if (e.has("mul")) {
-    auto& ops = e.get_arr("mul");
-    v.col = eval_dec_binary(t, 0, 4, 4, *ops[0], *ops[1]);
+  if (e.has("lit_f64")) {
+    v.is_lit = v.is_f64 = true;
+    v.f64 = lit_f64_value(e);
+    memcpy(&v.lit_lo, &v.f64, 8);
     return v;
   }
-  if (e.has("add")) {
-    auto& ops = e.get_arr("add");
-    v.col = eval_dec_binary(t, 1, 5, 5, *ops[0], *ops[1]);
-    return v;
-  }
-  if (e.has("sub")) {
-    auto& ops = e.get_arr("sub");
-    // col - lit == col + (-lit): negate the literal side
-    const Value& r = *ops[1];
-    if (r.has("lit") || r.kind == Value::INT || r.kind == Value::STR) {
-      ExprVal b = eval_expr(t, r);
-      if (b.is_lit) {
-        Value neg;  // synthesize -lit via direct call path
-        ExprVal a = eval_expr(t, *ops[0]);
-        if (a.is_lit) throw StageError(BG_ERR_INVALID, "sub of two literals");
-        __int128 litv = ((__int128)b.lit_hi << 64) | (uint64_t)b.lit_lo;
-        litv = -litv;
-        Col out = make_col({BG_DT_DECIMAL128, 38, a.col.scale});
-        out.data = dalloc_elems(t.n, 16);
-        bg_column ba = to_bg(a.col, t.n);
-        chk(bg_project_dec128(5, &ba, nullptr, (int64_t)(uint64_t)litv,
-                              (int64_t)(uint64_t)((unsigned __int128)litv >> 64),
-                              t.n, out.data->p),
-            "bg_project_dec128");
-        if (a.col.nullable()) out.validity = a.col.validity;
-        v.col = out;
-        return v;
-      }
+  for (const char* k : {"mul", "add", "sub", "div"})
+    if (e.has(k)) {
+      v.col = eval_arith(t, k, e);
+      return v;
     }
-    v.col = eval_dec_binary(t, 2, -1, 3, *ops[0], *ops[1]);
+  // CAST(arg AS to)  (q14/q17/q11/q20: sums to Float64 and back; q17/q22:
+  // Decimal128 rescale)
+  if (e.has("cast")) {
+    const Value& c = e.at("cast");
+    const DtSpec to = cast_target(c);
+    ExprVal a = eval_expr(t, c.at("arg"));
+    cast_check_pair(c, expr_spec(a), to);
+    Col out = make_col(to);
+    out.data = dalloc_elems(t.n, dt_size(to.dt));
+    bg_column ba = to_bg(a.col, t.n);
+    chk(bg_cast(&ba, to.dt, to.precision, to.scale, t.n, out.data->p,
+                nullptr),
+        "bg_cast");
+    share_validity(a.col, &out);
+    v.col = out;
     return v;
   }
   // CASE WHEN <predicates> THEN <expr> ELSE <expr>  (q8/q12/q14-class):
@@ -3063,7 +3263,7 @@ static DtSpec validate_expr(const VSchema& s, const Value& e);
 // node with the operand inside it, e.g. substr(c_phone)
 static std::string expr_label(const Value& e) {
   if (e.has("col")) return e.get_str("col");
-  for (const char* k : {"date_part", "substr"})
+  for (const char* k : {"date_part", "substr", "cast"})
     if (e.has(k))
       return std::string(k) + "(" + expr_label(e.at(k).at("arg")) + ")";
   return e.kind == Value::OBJ && !e.obj.empty() ? e.obj[0].first : "?";
@@ -3337,7 +3537,7 @@ static VSchema validate_plan(const Value& node) {
 
 static DtSpec validate_expr(const VSchema& s, const Value& e) {
   if (e.has("col")) return s.dts[(size_t)s.idx(e.get_str("col"))];
-  if (e.has("lit")) return {BG_DT_DECIMAL128, 38, 0};
+  if (e.has("lit")) return DT_LIT;
   if (e.has("case")) {
     const Value& c = e.at("case");
     validate_predicates(s, c.get_arr("when"));
@@ -3345,11 +3545,26 @@ static DtSpec validate_expr(const VSchema& s, const Value& e) {
     DtSpec b = validate_expr(s, c.at("else"));
     return a.dt == BG_DT_DECIMAL128 || b.dt != BG_DT_DECIMAL128 ? a : b;
   }
-  for (const char* k : {"mul", "add", "sub"}) {
+  if (e.has("lit_f64")) {
+    lit_f64_value(e);
+    return DT_F64;
+  }
+  if (e.has("cast")) {
+    const Value& c = e.at("cast");
+    const DtSpec to = cast_target(c);
+    cast_check_pair(c, validate_expr(s, c.at("arg")), to);
+    return to;
+  }
+  for (const char* k : {"mul", "add", "sub", "div"}) {
     if (e.has(k)) {
       auto& ops = e.get_arr(k);
+      if (ops.size() != 2)
+        throw StageError(BG_ERR_INVALID,
+                         std::string(k) + ": two operands required");
       DtSpec a = validate_expr(s, *ops[0]);
       DtSpec b = validate_expr(s, *ops[1]);
+      const ArithPlan p = arith_plan(k, e, *ops[0], a, *ops[1], b);
+      if (p.kind != ArithPlan::DEC128) return p.out;
       int scale = strcmp(k, "mul") == 0 ? a.scale + b.scale
                                         : (a.dt == BG_DT_DECIMAL128 ? a.scale
                                                                     : b.scale);

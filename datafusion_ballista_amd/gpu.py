@@ -72,6 +72,16 @@ BG_PROJ_RSUB_LIT = 3
 BG_PROJ_MUL_LIT = 4
 BG_PROJ_ADD_LIT = 5
 
+BG_F64_MUL = 0
+BG_F64_ADD = 1
+BG_F64_SUB = 2
+BG_F64_DIV = 3
+BG_F64_MUL_LIT = 4
+BG_F64_ADD_LIT = 5
+BG_F64_LIT_SUB = 6
+BG_F64_DIV_LIT = 7
+BG_F64_LIT_DIV = 8
+
 BG_LZ4_BLOCK = 65536
 BG_LZ4_SLOT_STRIDE = 65544
 LZ4_FRAME_HEADER = bytes.fromhex("04224d184040c0")  # magic+FLG+BD+HC
@@ -215,6 +225,8 @@ _SIGNATURES = {
     "bg_idx_sentinel": "i plpp", "bg_bitmap_and": "i pplp",
     "bg_hashagg": "i pippipllpppp", "bg_hashagg2": "i pippipllppppp",
     "bg_project_dec128": "i ipplllp",
+    "bg_cast": "i piiilpp", "bg_project_f64": "i ippdlp",
+    "bg_div_dec128": "i ppilpp",
     "bg_project_dec128_multi": "i pippipippilP", "bg_sort_rows": "i ppilp",
     "bg_sort_rows2": "i pppilp", "bg_merge_join": "i plplppp",
     "bg_snappy_decompress": "i plp", "bg_page_extract": "i plplllii",
@@ -494,6 +506,36 @@ class GpuStageContext:
         out = self.alloc(max(4 * n, 4))
         _check(self.L.bg_date_part(ctypes.byref(col), part, n, out.ptr),
                "bg_date_part")
+        return out
+
+    def cast(self, col: BgColumn, to_dtype: int, n: int, precision: int = 0,
+             scale: int = 0) -> DeviceBuffer:
+        """CAST(col AS to_dtype[(precision, scale)]) -> device buffer of n
+        target-width rows; shares the input's validity.  Raises with the
+        failed-row count when a valid row cannot be represented."""
+        out = self.alloc(max(_DT_SIZE.get(to_dtype, 16) * n, 16))
+        _check(self.L.bg_cast(ctypes.byref(col), to_dtype, precision, scale,
+                              n, out.ptr, None), "bg_cast")
+        return out
+
+    def project_f64(self, op: int, a: BgColumn, b: BgColumn, lit: float,
+                    n: int) -> DeviceBuffer:
+        """Float64 arithmetic (BG_F64_*): a OP b, or a OP lit with b None."""
+        out = self.alloc(max(8 * n, 8))
+        _check(self.L.bg_project_f64(op, ctypes.byref(a),
+                                     ctypes.byref(b) if b is not None
+                                     else None, lit, n, out.ptr),
+               "bg_project_f64")
+        return out
+
+    def div_dec128(self, a: BgColumn, b: BgColumn, mul_pow: int,
+                   n: int) -> DeviceBuffer:
+        """Decimal128 a / b after scale alignment by 10^mul_pow, truncated
+        toward zero.  Raises on a zero divisor or an i128 overflow in a row
+        valid in both inputs."""
+        out = self.alloc(max(16 * n, 16))
+        _check(self.L.bg_div_dec128(ctypes.byref(a), ctypes.byref(b), mul_pow,
+                                    n, out.ptr, None), "bg_div_dec128")
         return out
 
     def substr(self, col: BgColumn, start: int, count: int = None,

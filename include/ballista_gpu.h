@@ -244,6 +244,74 @@ int bg_eval_in_utf8(const bg_column* col, const char* const* values,
                     const int32_t* value_lens, int32_t nvalues, int64_t n,
                     uint8_t* d_mask);
 
+/* ---- CAST, Float64 arithmetic and Decimal128 division.  Some of these can
+ * fail on a row, as they fail the query in DataFusion (casts run with
+ * safe=false, decimal division raises DivideByZero).  A fallible call counts
+ * the failing VALID rows, returns BG_ERR_INVALID with a message naming the
+ * failure and the count ("cast: 3 of 1000 rows overflow Decimal128(19,6)",
+ * "div: division by zero in 1 row") and stores the count to *out_failed
+ * (may be NULL; 0 on success).  d_out is then unspecified.  Rows that are
+ * NULL by the input validity are never examined: a zero divisor or garbage
+ * under a NULL fails nothing.  The output's validity is the input's (the
+ * AND of both inputs' for a binary call); the caller shares or combines
+ * the bitmaps. ---- */
+
+/* CAST(src AS to_dtype[(to_precision, to_scale)]).  d_out: n rows of the
+ * target's width.  Pairs:
+ *  - INT32 / INT64 / DECIMAL128(p,s) -> FLOAT64 (approved/q14.txt:22,
+ *    q17.txt:27,33, q11.txt:70, q20.txt:49: CAST(sum(..) AS Float64)).
+ *    Integers as (double)x; a decimal as (double)x / P10[s], where
+ *    (double) of the i128 rounds once to nearest-even and P10 is the table
+ *    of the correctly rounded doubles 1e0..1e38.  arrow-rs computes
+ *    x as f64 / 10f64.powi(s): identical for s <= 22, where every power is
+ *    exact; beyond that powi may differ from the table in the last bit,
+ *    which has not been compared against a Rust build.
+ *  - FLOAT64 -> DECIMAL128(p,s) (q17.txt:27, q11.txt:70):
+ *    r = round(v * P10[s]) with C round() (half away from zero); a row
+ *    fails when v is NaN or +-inf or |r| >= 10^p.
+ *  - DECIMAL128(p1,s1) -> DECIMAL128(p2,s2) (q17.txt:19, q11.txt:74,
+ *    q22.txt:18): x * 10^(s2-s1) for s2 >= s1, else x / 10^(s1-s2) rounded
+ *    half away from zero (arrow-rs decimal-to-decimal); a row fails when
+ *    |result| >= 10^p2.
+ *  - INT32 / INT64 -> DECIMAL128(p,s): x * 10^s, same check.
+ *  - INT32 -> INT64.
+ * Any other pair returns BG_ERR_UNSUPPORTED before anything is allocated.
+ * A conversion that cannot fail launches no failure counter and reads
+ * nothing back: anything to FLOAT64, INT32 -> INT64, and a decimal target
+ * wide enough for every input of the source's declared precision (10 and
+ * 19 digits for INT32 / INT64; a source precision outside 1..38 counts as
+ * unknown and is checked). */
+int bg_cast(const bg_column* src, int32_t to_dtype, int32_t to_precision,
+            int32_t to_scale, int64_t n, void* d_out, int64_t* out_failed);
+
+/* Float64 arithmetic (q14.txt:22: 100 * a / b; q17.txt:33: a / 7;
+ * q17.txt:27, q20.txt:49: 0.2 * a, 0.5 * a; q11.txt:70: a * 0.0001).  Each
+ * result is exactly one IEEE-754 binary64 operation; division by zero
+ * yields inf or NaN as arrow's float div does and is no failure.  The
+ * column ops take a and b, the literal ops take a and lit (b ignored).  A
+ * non-FLOAT64 column returns BG_ERR_INVALID. */
+#define BG_F64_MUL 0     /* a * b */
+#define BG_F64_ADD 1     /* a + b */
+#define BG_F64_SUB 2     /* a - b */
+#define BG_F64_DIV 3     /* a / b */
+#define BG_F64_MUL_LIT 4 /* a * lit */
+#define BG_F64_ADD_LIT 5 /* a + lit */
+#define BG_F64_LIT_SUB 6 /* lit - a */
+#define BG_F64_DIV_LIT 7 /* a / lit */
+#define BG_F64_LIT_DIV 8 /* lit / a */
+int bg_project_f64(int32_t op, const bg_column* a, const bg_column* b,
+                   double lit, int64_t n, double* d_out);
+
+/* Decimal128 / Decimal128 (q8.txt:103: sum(case..) / sum(volume) as
+ * mkt_share), arrow-rs's decimal div: plain i128 division, truncated toward
+ * zero, after aligning scales.  mul_pow >= 0: (a * 10^mul_pow) / b;
+ * mul_pow < 0: a / (b * 10^-mul_pow); for a result of scale S over inputs
+ * of scales s1 and s2, mul_pow = S - s1 + s2.  A valid row (valid in a AND
+ * in b) fails when b == 0 or when the scaled operand leaves i128.  d_out:
+ * n x 16 B.  |mul_pow| > 38 or a non-DECIMAL128 column: BG_ERR_INVALID. */
+int bg_div_dec128(const bg_column* a, const bg_column* b, int32_t mul_pow,
+                  int64_t n, void* d_out, int64_t* out_failed);
+
 /* ---- hash repartition (SortShuffleWriterExec device half) ---- */
 
 /* create_hashes restatement over the key columns (bg_ahash.h; parity
