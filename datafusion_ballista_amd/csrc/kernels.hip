@@ -7104,6 +7104,149 @@ __global__ void k_join_mark2(JoinProbeArgs t, Filter f, uint32_t* visited) {
     });
 }
 
+// ---------------------------------------------------------------------------
+// Nested-loop join (NestedLoopJoinExec, datafusion.proto:1359-1365;
+// approved/q11.txt:69, q22.txt:14): a join without keys, so EVERY build row
+// is a candidate of every probe row and the residual filter alone decides.
+// It is the general probe above with a plain loop over the build rows in
+// place of the chain walk: the same filter policies, the same count ->
+// exclusive scan -> fill scheme, the same visited bitmap and the same
+// join-type helpers.
+//
+// Lanes own probe rows; the build index b runs 0 .. n_build-1 in a loop
+// whose control is wave-uniform, so a build row's mask bit, value and
+// validity sit at one address per wave, and the probe row's operands do not
+// change across the loop.  Whole waves iterate: a lane past n_probe stays
+// in with active = false, which makes marking build row b one ballot and one
+// mark_visited by lane 0 instead of up to 64 lanes contending on one word.
+// Parallelism is over probe rows only: a one-row probe side against a large
+// build side runs serially in one lane (DataFusion puts the smaller input
+// on the build side, so the approved plans never have that shape).
+// ---------------------------------------------------------------------------
+
+// the groups some lane of this wave is still live in
+__device__ __forceinline__ uint32_t jf_wave_groups(int ngroups, uint32_t live) {
+  uint32_t any = 0;
+  for (int g = 0; g < ngroups; ++g)
+    if (__ballot((live >> g) & 1) != 0) any |= 1u << g;
+  return any;
+}
+
+// What the nested-loop walk asks of a filter policy beyond live() and
+// passes(): the groups live anywhere in the wave (0 = the wave walks
+// nothing), and whether build row b can pass in one of them, which is one
+// wave-uniform test because b is.
+__device__ __forceinline__ uint32_t nl_wave_groups(const JoinNoFilter&,
+                                                   uint32_t live) {
+  return __ballot(live != 0) != 0;
+}
+__device__ __forceinline__ uint32_t nl_wave_groups(const JoinFiltered& f,
+                                                   uint32_t live) {
+  return jf_wave_groups(f.f.ngroups, live);
+}
+__device__ __forceinline__ bool nl_build_live(const JoinNoFilter&, uint32_t,
+                                              int64_t) {
+  return true;
+}
+__device__ __forceinline__ bool nl_build_live(const JoinFiltered& f,
+                                              uint32_t groups, int64_t b) {
+  for (int g = 0; g < f.f.ngroups; ++g)
+    if (((groups >> g) & 1) && bit_valid(f.f.g[g].build_mask, b)) return true;
+  return false;
+}
+
+// THE nested-loop walk of probe row i (active: i is a row of this launch):
+// calls match(build row) for every build row the filter passes, in ascending
+// build order, until match returns true ("stop"), the contract of join_walk.
+// Every lane of the wave must call it; the wave leaves the loop when no lane
+// still wants candidates.  A probe row with no live group walks nothing, a
+// build row whose masks clear every group live in the wave is skipped by
+// all of it.  There are no keys, so the only NULL rule is the filter's.
+// MARK sets the visited bit of every build row some lane matched.  Count,
+// fill and mark all go through here, so they see the same matches in the
+// same order.
+template <bool MARK, typename Filter, typename Match>
+__device__ __forceinline__ void nl_join_walk(int64_t n_build, const Filter& f,
+                                             int64_t i, bool active,
+                                             uint32_t* visited,
+                                             Match&& match) {
+  const uint32_t live = active ? f.live(i) : 0;
+  bool want = live != 0;
+  const uint32_t groups = nl_wave_groups(f, live);
+  if (!groups) return;
+  for (int64_t b = 0; b < n_build && __ballot(want) != 0; ++b) {
+    if (!nl_build_live(f, groups, b)) continue;
+    const bool hit = want && f.passes(live, b, i);
+    if (MARK && __ballot(hit) != 0 && lane_id() == 0)
+      mark_visited(visited, b);
+    if (hit) want = !match(b);
+  }
+}
+
+struct NlJoinArgs {
+  int64_t n_build, n_probe;
+};
+
+// Pair order of the nested-loop fill: ascending probe row, and within a
+// probe row ascending build row; an unmatched probe row (ANTI / OUTER_PROBE)
+// carries BG_JOIN_NULL_IDX.  The grid-stride loops below step by whole
+// blocks, so every wave enters the walk complete.
+template <typename Filter>
+__global__ void k_nl_join_count(NlJoinArgs t, int32_t join_type, Filter f,
+                                uint32_t* counts) {
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < t.n_probe;
+       base += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = base + threadIdx.x;
+    const bool active = i < t.n_probe;
+    u64 cnt = 0;
+    nl_join_walk<false>(t.n_build, f, i, active, nullptr, [&](int64_t) {
+      ++cnt;
+      return join_first_match_decides(join_type);
+    });
+    if (!join_emits_matches(join_type)) cnt = cnt ? 0 : 1;
+    else if (join_emits_unmatched_probe(join_type)) cnt = cnt ? cnt : 1;
+    if (active) counts[i] = (uint32_t)cnt;
+  }
+}
+
+// Writes the pairs k_nl_join_count counted for the same join_type and
+// filter.  MARK as in k_join_fill2: INNER and OUTER_PROBE pairs only.
+template <typename Filter, bool MARK>
+__global__ void k_nl_join_fill(NlJoinArgs t, int32_t join_type, Filter f,
+                               const i64* offsets, uint32_t* out_probe,
+                               uint32_t* out_build, uint32_t* visited) {
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < t.n_probe;
+       base += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = base + threadIdx.x;
+    const bool active = i < t.n_probe;
+    i64 w = active ? offsets[i] : 0;
+    bool matched = false;
+    nl_join_walk<MARK>(t.n_build, f, i, active, visited, [&](int64_t b) {
+      matched = true;
+      if (!MARK && !join_emits_matches(join_type)) return true;
+      out_probe[w] = (uint32_t)i;
+      out_build[w] = (uint32_t)b;
+      ++w;
+      return !MARK && join_first_match_decides(join_type);
+    });
+    if (active && !matched && join_emits_unmatched_probe(join_type)) {
+      out_probe[w] = (uint32_t)i;
+      out_build[w] = BG_JOIN_NULL_IDX;
+    }
+  }
+}
+
+// Marks every matched build row and emits nothing: walks every build row.
+template <typename Filter>
+__global__ void k_nl_join_mark(NlJoinArgs t, Filter f, uint32_t* visited) {
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < t.n_probe;
+       base += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = base + threadIdx.x;
+    nl_join_walk<true>(t.n_build, f, i, i < t.n_probe, visited,
+                       [&](int64_t) { return false; });
+  }
+}
+
 // ~visited (or all ones where nothing was ever marked) as a mask for the
 // stable compaction, which trims the bits at or beyond n itself
 __global__ void k_bitmap_not_u64(const u64* in, int64_t nwords, u64* out) {
@@ -7161,7 +7304,8 @@ static inline uint64_t join_visited_bytes(int64_t n_build) {
 
 // lazily allocate + zero the visited bitmap (stream-ordered memset: every
 // marking kernel is launched on the same null stream after it)
-static int join_ensure_visited(BgJoinTable2* t) {
+template <typename Table>
+static int join_ensure_visited(Table* t) {
   if (t->visited) return BG_OK;
   DevBuf<uint8_t> v;
   HIP_TRY(v.alloc((int64_t)join_visited_bytes(t->n_build)));
@@ -7258,11 +7402,11 @@ extern "C" int bg_hashjoin_free2(void* handle) {
   return BG_OK;
 }
 
-extern "C" int bg_hashjoin_build_rows2(void* handle, int32_t matched,
-                                       int64_t* out_count,
-                                       uint32_t* d_out_build) {
-  REQUIRE_INIT();
-  BgJoinTable2* t = (BgJoinTable2*)handle;
+// The build rows of either visited-bitmap handle whose bit == matched, in
+// ascending build order; bits at or beyond n_build are never reported.
+template <typename Table>
+static int join_build_rows(Table* t, int32_t matched, int64_t* out_count,
+                           uint32_t* d_out_build) {
   if (!t || !out_count)
     return set_err(BG_ERR_INVALID, "null join handle / out_count");
   if (matched != 0 && matched != 1)
@@ -7283,6 +7427,14 @@ extern "C" int bg_hashjoin_build_rows2(void* handle, int32_t matched,
   HIP_TRY(hipGetLastError());
   return mask_to_indices(reinterpret_cast<const uint8_t*>(inv.get()),
                          t->n_build, d_out_build, out_count);
+}
+
+extern "C" int bg_hashjoin_build_rows2(void* handle, int32_t matched,
+                                       int64_t* out_count,
+                                       uint32_t* d_out_build) {
+  REQUIRE_INIT();
+  return join_build_rows((BgJoinTable2*)handle, matched, out_count,
+                         d_out_build);
 }
 
 // flat ABI terms -> the kernels' grouped program, every limit checked
@@ -7495,6 +7647,162 @@ extern "C" int bg_hashjoin_probe_mark2_filtered(
   if (rc == BG_OK) rc = join_filter_args(terms, nterms, t->n_build, n, &f);
   if (rc != BG_OK) return rc;
   return join_mark(t, a, &f);
+}
+
+// ---- nested-loop join: host side ----
+// The handle owns what the general hash-join handle owns minus the table:
+// the offsets between count and fill, and the visited bitmap.
+struct BgNlJoin {
+  int64_t n_build = 0;
+  i64* probe_offsets = nullptr;
+  int64_t probe_n = 0;
+  int32_t probe_jt = -1;  // JOIN_JT_FILTERED set: counted with probe_filter
+  uint32_t* visited = nullptr;
+  JoinFilterArgs probe_filter = {};
+};
+
+// What every bg_nljoin_* probe entry checks first, before anything is
+// allocated or launched; terms == none (nterms 0) is a cross join.
+// *has_filter tells whether *f was filled.
+static int nljoin_check(void* handle, int64_t n_probe,
+                        const bg_join_filter_term* terms, int32_t nterms,
+                        JoinFilterArgs* f, bool* has_filter) {
+  const BgNlJoin* t = (const BgNlJoin*)handle;
+  if (!t) return set_err(BG_ERR_INVALID, "null nested-loop join handle");
+  if (n_probe < 0)
+    return set_err(BG_ERR_INVALID, "nested-loop join: negative n_probe");
+  if (nterms < 0)
+    return set_err(BG_ERR_INVALID, "nested-loop join: negative nterms");
+  *has_filter = nterms > 0;
+  if (nterms == 0) return BG_OK;
+  return join_filter_args(terms, nterms, t->n_build, n_probe, f);
+}
+
+static int nljoin_check_pair_type(int32_t jt) {
+  if (jt == BG_JOIN_SEMI_BUILD || jt == BG_JOIN_ANTI_BUILD)
+    return set_err(BG_ERR_INVALID,
+                   "SEMI_BUILD/ANTI_BUILD emit no pairs: call "
+                   "bg_nljoin_mark, then bg_nljoin_build_rows");
+  if (jt < BG_JOIN_INNER || jt > BG_JOIN_OUTER_FULL)
+    return set_err(BG_ERR_INVALID, "unknown join_type");
+  return BG_OK;
+}
+
+extern "C" int bg_nljoin_open(int64_t n_build, void** out_handle) {
+  REQUIRE_INIT();
+  if (!out_handle) return set_err(BG_ERR_INVALID, "null out_handle");
+  if (n_build < 0)
+    return set_err(BG_ERR_INVALID, "nested-loop join: negative n_build");
+  // build rows travel as u32 indices and BG_JOIN_NULL_IDX is taken
+  if (n_build >= 0xFFFFFFFFLL)
+    return set_err(BG_ERR_INVALID,
+                   "nested-loop join: build side >= 2^32 - 1 rows");
+  BgNlJoin* t = new BgNlJoin();
+  t->n_build = n_build;
+  *out_handle = t;
+  return BG_OK;
+}
+
+extern "C" int bg_nljoin_free(void* handle) {
+  REQUIRE_INIT();
+  BgNlJoin* t = (BgNlJoin*)handle;
+  if (!t) return BG_OK;
+  if (t->probe_offsets) (void)pool_release(t->probe_offsets);
+  if (t->visited) (void)pool_release(t->visited);
+  delete t;
+  return BG_OK;
+}
+
+extern "C" int bg_nljoin_count(void* handle, int64_t n_probe,
+                               int32_t join_type,
+                               const bg_join_filter_term* terms,
+                               int32_t nterms, int64_t* out_matches) {
+  REQUIRE_INIT();
+  BgNlJoin* t = (BgNlJoin*)handle;
+  JoinFilterArgs f;
+  bool filtered = false;
+  int rc = nljoin_check(handle, n_probe, terms, nterms, &f, &filtered);
+  if (rc == BG_OK) rc = nljoin_check_pair_type(join_type);
+  if (rc != BG_OK) return rc;
+  if (!out_matches) return set_err(BG_ERR_INVALID, "null out_matches");
+  const NlJoinArgs a{t->n_build, n_probe};
+  rc = join_count_phase(t, n_probe, out_matches, [&](uint32_t* counts) {
+    join_with_filter(filtered ? &f : nullptr, [&](auto filter) {
+      hipLaunchKernelGGL(k_nl_join_count<decltype(filter)>,
+                         dim3(grid_for(n_probe)), dim3(BG_BLOCK), 0, 0, a,
+                         join_pair_type(join_type), filter, counts);
+    });
+  });
+  if (rc != BG_OK) return rc;
+  // a fill must repeat the type and, with JOIN_JT_FILTERED, the filter
+  t->probe_jt = filtered ? join_type | JOIN_JT_FILTERED : join_type;
+  if (filtered) t->probe_filter = f;
+  return BG_OK;
+}
+
+extern "C" int bg_nljoin_fill(void* handle, int64_t n_probe,
+                              int32_t join_type,
+                              const bg_join_filter_term* terms,
+                              int32_t nterms, uint32_t* d_out_probe,
+                              uint32_t* d_out_build) {
+  REQUIRE_INIT();
+  BgNlJoin* t = (BgNlJoin*)handle;
+  JoinFilterArgs f;
+  bool filtered = false;
+  int rc = nljoin_check(handle, n_probe, terms, nterms, &f, &filtered);
+  if (rc == BG_OK) rc = nljoin_check_pair_type(join_type);
+  if (rc != BG_OK) return rc;
+  // the offsets are only good for the type and filter they were counted under
+  if (!t->probe_offsets || t->probe_n != n_probe ||
+      t->probe_jt != (filtered ? join_type | JOIN_JT_FILTERED : join_type) ||
+      (filtered && memcmp(&f, &t->probe_filter, sizeof(f)) != 0))
+    return set_err(BG_ERR_INVALID,
+                   "call bg_nljoin_count first (same n_probe, same "
+                   "join_type, same terms)");
+  const bool mark = join_type_marks(join_type);
+  if (mark) {
+    rc = join_ensure_visited(t);
+    if (rc != BG_OK) return rc;
+  }
+  const NlJoinArgs a{t->n_build, n_probe};
+  join_with_filter(filtered ? &f : nullptr, [&](auto filter) {
+    using F = decltype(filter);
+    hipLaunchKernelGGL(
+        (mark ? k_nl_join_fill<F, true> : k_nl_join_fill<F, false>),
+        dim3(grid_for(n_probe)), dim3(BG_BLOCK), 0, 0, a,
+        join_pair_type(join_type), filter, t->probe_offsets, d_out_probe,
+        d_out_build, t->visited);
+  });
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+extern "C" int bg_nljoin_mark(void* handle, int64_t n_probe,
+                              const bg_join_filter_term* terms,
+                              int32_t nterms) {
+  REQUIRE_INIT();
+  BgNlJoin* t = (BgNlJoin*)handle;
+  JoinFilterArgs f;
+  bool filtered = false;
+  int rc = nljoin_check(handle, n_probe, terms, nterms, &f, &filtered);
+  if (rc == BG_OK) rc = join_ensure_visited(t);
+  if (rc != BG_OK) return rc;
+  if (n_probe == 0) return BG_OK;
+  const NlJoinArgs a{t->n_build, n_probe};
+  join_with_filter(filtered ? &f : nullptr, [&](auto filter) {
+    hipLaunchKernelGGL(k_nl_join_mark<decltype(filter)>,
+                       dim3(grid_for(n_probe)), dim3(BG_BLOCK), 0, 0, a,
+                       filter, t->visited);
+  });
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+extern "C" int bg_nljoin_build_rows(void* handle, int32_t matched,
+                                    int64_t* out_count,
+                                    uint32_t* d_out_build) {
+  REQUIRE_INIT();
+  return join_build_rows((BgNlJoin*)handle, matched, out_count, d_out_build);
 }
 
 // sentinel handling for probe-outer joins: split an index vector carrying

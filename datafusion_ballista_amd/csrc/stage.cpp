@@ -1786,17 +1786,30 @@ static const JoinKind JOIN_KINDS[] = {
     {"full", BG_JOIN_OUTER_FULL, false, true, true},
 };
 
+// Both join nodes (hash_join, nested_loop_join) read the list; a refusal
+// names the node it came from.
 static const JoinKind& join_kind(const Value& node) {
   const std::string jt = node.get_str_or("join_type", "inner");
   for (auto& k : JOIN_KINDS)
     if (jt == k.name) return k;
-  throw StageError(BG_ERR_UNSUPPORTED, "hash_join: join_type " + jt);
+  throw StageError(BG_ERR_UNSUPPORTED,
+                   node.get_str("op") + ": join_type " + jt);
 }
 
-static void require_build_side(const std::string& jt, const Value& o) {
+// nested_loop_join is the keyless join: keys on it are a mistake, not a hint
+static void refuse_join_keys(const Value& node) {
+  for (const char* key : {"build_keys", "probe_keys"})
+    if (node.has(key))
+      throw StageError(BG_ERR_INVALID,
+                       std::string("nested_loop_join: '") + key +
+                           "' given; a join with keys is a hash_join");
+}
+
+static void require_build_side(const std::string& op, const std::string& jt,
+                               const Value& o) {
   if (o.get_str("side") != "build")
     throw StageError(BG_ERR_INVALID,
-                     "hash_join: " + jt + " emits build rows only; output '" +
+                     op + ": " + jt + " emits build rows only; output '" +
                          o.get_str("col") + "' is not side 'build'");
 }
 
@@ -1805,42 +1818,56 @@ struct JoinOut {
   std::string col, as;
 };
 
-// One entry of a join node's "output" list, checked against the join type.
-static JoinOut join_output(const JoinKind& k, const Value& o) {
-  if (k.build_rows_only) require_build_side(k.name, o);
+// One entry of a join node's "output" list, checked against the join type;
+// op names the node in the message.
+static JoinOut join_output(const std::string& op, const JoinKind& k,
+                           const Value& o) {
+  if (k.build_rows_only) require_build_side(op, k.name, o);
   const bool build = o.get_str("side") == "build";
   const std::string col = o.get_str("col");
   return {build, col, o.get_str_or("as", col)};
 }
 
-// The hash table of one join: the single-INT64-key inner join without a
-// residual filter has a specialised table, every other shape goes through
-// the general one.  The probe calls take the chunk's filter terms; none
+// The library handle of one join.  With build keys it is a hash table: the
+// single-INT64-key inner join without a residual filter has a specialised
+// one, every other keyed shape goes through the general one.  Without keys
+// (nested_loop_join) it is the nested-loop handle, which holds no table and
+// takes no probe keys.  The probe calls take the chunk's filter terms; none
 // means no filter.
 using JoinTerms = std::vector<bg_join_filter_term>;
 struct JoinHandle {
   void* h = nullptr;
+  const bool nl;  // no keys: bg_nljoin_*
   const bool fast;
   const int32_t type;
   JoinHandle(const JoinHandle&) = delete;
   JoinHandle& operator=(const JoinHandle&) = delete;
+  // bk empty: a nested-loop join
   JoinHandle(const std::vector<bg_column>& bk, int64_t n, int32_t join_type,
              bool filtered)
-      : fast(bk.size() == 1 && bk[0].dtype == BG_DT_INT64 &&
+      : nl(bk.empty()),
+        fast(bk.size() == 1 && bk[0].dtype == BG_DT_INT64 &&
              join_type == BG_JOIN_INNER && !filtered),
         type(join_type) {
-    if (fast) chk(bg_hashjoin_build(&bk[0], n, &h), "bg_hashjoin_build");
+    if (nl) chk(bg_nljoin_open(n, &h), "bg_nljoin_open");
+    else if (fast) chk(bg_hashjoin_build(&bk[0], n, &h), "bg_hashjoin_build");
     else
       chk(bg_hashjoin_build2(bk.data(), (int32_t)bk.size(), n, &h),
           "bg_hashjoin_build2");
   }
   ~JoinHandle() {
-    if (h) (void)(fast ? bg_hashjoin_free(h) : bg_hashjoin_free2(h));
+    if (!h) return;
+    (void)(nl ? bg_nljoin_free(h)
+              : fast ? bg_hashjoin_free(h) : bg_hashjoin_free2(h));
   }
   int64_t count(const std::vector<bg_column>& pk, int64_t len,
                 const JoinTerms& ft) {
     int64_t matches = 0;
-    if (fast)
+    if (nl)
+      chk(bg_nljoin_count(h, len, type, ft.data(), (int32_t)ft.size(),
+                          &matches),
+          "bg_nljoin_count");
+    else if (fast)
       chk(bg_hashjoin_probe_count(h, &pk[0], len, &matches),
           "bg_hashjoin_probe_count");
     else if (ft.empty())
@@ -1856,7 +1883,11 @@ struct JoinHandle {
   }
   void fill(const std::vector<bg_column>& pk, int64_t len,
             const JoinTerms& ft, uint32_t* pidx, uint32_t* bidx) {
-    if (fast)
+    if (nl)
+      chk(bg_nljoin_fill(h, len, type, ft.data(), (int32_t)ft.size(), pidx,
+                         bidx),
+          "bg_nljoin_fill");
+    else if (fast)
       chk(bg_hashjoin_probe_fill(h, &pk[0], len, pidx, bidx),
           "bg_hashjoin_probe_fill");
     else if (ft.empty())
@@ -1869,11 +1900,14 @@ struct JoinHandle {
                                            (int32_t)ft.size(), pidx, bidx),
           "bg_hashjoin_probe_fill2_filtered");
   }
-  // the build-rows calls exist for the general table only; the types that
-  // use them never take the fast path
+  // the build-rows calls exist for the general table and the nested-loop
+  // handle only; the types that use them never take the fast path
   void mark(const std::vector<bg_column>& pk, int64_t len,
             const JoinTerms& ft) {
-    if (ft.empty())
+    if (nl)
+      chk(bg_nljoin_mark(h, len, ft.data(), (int32_t)ft.size()),
+          "bg_nljoin_mark");
+    else if (ft.empty())
       chk(bg_hashjoin_probe_mark2(h, pk.data(), (int32_t)pk.size(), len),
           "bg_hashjoin_probe_mark2");
     else
@@ -1885,8 +1919,12 @@ struct JoinHandle {
   // ascending build order
   int64_t build_rows(int matched, uint32_t* idx) {
     int64_t rows = 0;
-    chk(bg_hashjoin_build_rows2(h, matched, &rows, idx),
-        "bg_hashjoin_build_rows2");
+    if (nl)
+      chk(bg_nljoin_build_rows(h, matched, &rows, idx),
+          "bg_nljoin_build_rows");
+    else
+      chk(bg_hashjoin_build_rows2(h, matched, &rows, idx),
+          "bg_hashjoin_build_rows2");
     return rows;
   }
 };
@@ -2039,9 +2077,10 @@ static int64_t join_probe_chunk(JoinHandle& jh, const JoinKind& k,
     const JoinOut& o = s.outs[oi];
     const bool outer_build = o.build && k.probe_null_idx;
     Col c;
-    if (outer_build && k.type == BG_JOIN_OUTER_FULL && s.build.n == 0) {
-      // full join over an empty build side: every pair is an unmatched
-      // probe row, and there is no build row 0 to gather a filler from
+    if (outer_build && s.build.n == 0) {
+      // left or full join over an empty build side: every pair is an
+      // unmatched probe row, and there is no build row 0 to gather a filler
+      // from
       c = null_col(s.build.col(o.col), matches);
     } else if (o.build) {
       c = s.gather_build(o.col, outer_build ? bidx_clamped : bidx, matches);
@@ -2082,9 +2121,16 @@ static Table exec_join(const Value& node, Metrics& m) {
   JoinSides s;
   s.build = exec_plan(node.at("build"), m);
   s.probe = exec_plan(node.at("probe"), m);
-  auto& bkeys = node.get_arr("build_keys");
-  auto& pkeys = node.get_arr("probe_keys");
-  if (bkeys.size() != pkeys.size() || bkeys.empty() || bkeys.size() > 4)
+  const std::string op = node.get_str("op");
+  // nested_loop_join has no keys: bk stays empty, which is what tells the
+  // handle below to be the nested-loop one
+  static const std::vector<bgjson::ValuePtr> no_keys;
+  const bool keyed = op == "hash_join";
+  if (!keyed) refuse_join_keys(node);
+  auto& bkeys = keyed ? node.get_arr("build_keys") : no_keys;
+  auto& pkeys = keyed ? node.get_arr("probe_keys") : no_keys;
+  if (keyed &&
+      (bkeys.size() != pkeys.size() || bkeys.empty() || bkeys.size() > 4))
     throw StageError(BG_ERR_INVALID, "hash_join: 1-4 matching key columns");
   const JoinKind& k = join_kind(node);
 
@@ -2095,7 +2141,8 @@ static Table exec_join(const Value& node, Metrics& m) {
     if (bk[i].dtype != s.probe.cols[(size_t)s.pk_ids[i]].dtype)
       throw StageError(BG_ERR_INVALID, "hash_join: key dtype mismatch");
   }
-  for (auto& o : node.get_arr("output")) s.outs.push_back(join_output(k, *o));
+  for (auto& o : node.get_arr("output"))
+    s.outs.push_back(join_output(op, k, *o));
   s.eval_filter(node);
   JoinHandle jh(bk, s.build.n, k.type, !s.filter.empty());
 
@@ -2578,7 +2625,8 @@ static Table exec_plan(const Value& node, Metrics& m) {
     return filter_materialize(in, eval_filter_node(in, node));
   }
   if (op == "project") return exec_project(node, m);
-  if (op == "hash_join") return exec_join(node, m);
+  if (op == "hash_join" || op == "nested_loop_join")
+    return exec_join(node, m);
   if (op == "hash_aggregate") return exec_aggregate(node, m);
   if (op == "sort") return exec_sort(node, m);
   if (op == "limit") {
@@ -3342,7 +3390,8 @@ static bool schema_has(const VSchema& s, const std::string& n) {
 
 // one side's predicate list of a join filter group: the ordinary pred
 // grammar, over that side's columns only
-static void validate_join_filter_side(const VSchema& own, const VSchema& other,
+static void validate_join_filter_side(const std::string& op,
+                                      const VSchema& own, const VSchema& other,
                                       const char* side, const char* other_side,
                                       const Value& preds) {
   for (auto& p : preds.arr) {
@@ -3352,7 +3401,7 @@ static void validate_join_filter_side(const VSchema& own, const VSchema& other,
       if (!schema_has(own, n))
         throw StageError(
             BG_ERR_INVALID,
-            std::string("hash_join filter: '") + side + "' predicate names '" +
+            op + " filter: '" + side + "' predicate names '" +
                 n + "', " +
                 (schema_has(other, n)
                      ? std::string("a column of the ") + other_side + " side"
@@ -3361,28 +3410,29 @@ static void validate_join_filter_side(const VSchema& own, const VSchema& other,
   }
 }
 
-// hash_join "filter": {"any": [{build?, probe?, cross?}...]}; b and p are
-// the build and probe schemas
-static void validate_join_filter(const VSchema& b, const VSchema& p,
-                                 const Value& filt) {
+// A join node's "filter": {"any": [{build?, probe?, cross?}...]}; op is the
+// node's name (hash_join, nested_loop_join), b and p are the build and probe
+// schemas
+static void validate_join_filter(const std::string& op, const VSchema& b,
+                                 const VSchema& p, const Value& filt) {
   auto& groups = filt.get_arr("any");
   if (groups.empty())
     throw StageError(BG_ERR_INVALID,
-                     "hash_join filter: empty 'any' (omit the filter)");
+                     op + " filter: empty 'any' (omit the filter)");
   if (groups.size() > BG_JOIN_FILTER_MAX_GROUPS)
     throw StageError(BG_ERR_UNSUPPORTED,
-                     "hash_join filter: " + std::to_string(groups.size()) +
+                     op + " filter: " + std::to_string(groups.size()) +
                          " groups in 'any', at most 4");
   for (size_t gi = 0; gi < groups.size(); ++gi) {
     const Value& g = *groups[gi];
-    const std::string where = "hash_join filter: group " + std::to_string(gi);
+    const std::string where = op + " filter: group " + std::to_string(gi);
     size_t nterms = 0;
     if (g.has("build")) {
-      validate_join_filter_side(b, p, "build", "probe", g.at("build"));
+      validate_join_filter_side(op, b, p, "build", "probe", g.at("build"));
       nterms += g.get_arr("build").size();
     }
     if (g.has("probe")) {
-      validate_join_filter_side(p, b, "probe", "build", g.at("probe"));
+      validate_join_filter_side(op, p, b, "probe", "build", g.at("probe"));
       nterms += g.get_arr("probe").size();
     }
     if (g.has("cross")) {
@@ -3477,16 +3527,20 @@ static VSchema validate_plan(const Value& node) {
     }
     return out;
   }
-  if (op == "hash_join") {
+  if (op == "hash_join" || op == "nested_loop_join") {
     VSchema b = validate_plan(node.at("build"));
     VSchema p = validate_plan(node.at("probe"));
-    for (auto& k : node.get_arr("build_keys")) b.idx(k->s);
-    for (auto& k : node.get_arr("probe_keys")) p.idx(k->s);
+    if (op == "hash_join") {
+      for (auto& k : node.get_arr("build_keys")) b.idx(k->s);
+      for (auto& k : node.get_arr("probe_keys")) p.idx(k->s);
+    } else {
+      refuse_join_keys(node);
+    }
     const JoinKind& k = join_kind(node);
-    if (node.has("filter")) validate_join_filter(b, p, node.at("filter"));
+    if (node.has("filter")) validate_join_filter(op, b, p, node.at("filter"));
     VSchema out;
     for (auto& ov : node.get_arr("output")) {
-      const JoinOut o = join_output(k, *ov);
+      const JoinOut o = join_output(op, k, *ov);
       const VSchema& src = o.build ? b : p;
       out.dts.push_back(src.dts[(size_t)src.idx(o.col)]);
       out.names.push_back(o.as);

@@ -222,6 +222,9 @@ _SIGNATURES = {
     "bg_hashjoin_probe_count2_filtered": "i ppilipip",
     "bg_hashjoin_probe_fill2_filtered": "i ppilipipp",
     "bg_hashjoin_probe_mark2_filtered": "i ppilpi",
+    "bg_nljoin_open": "i lP", "bg_nljoin_count": "i plipip",
+    "bg_nljoin_fill": "i plipipp", "bg_nljoin_mark": "i plpi",
+    "bg_nljoin_build_rows": "i pipp", "bg_nljoin_free": "i p",
     "bg_idx_sentinel": "i plpp", "bg_bitmap_and": "i pplp",
     "bg_hashagg": "i pippipllpppp", "bg_hashagg2": "i pippipllppppp",
     "bg_project_dec128": "i ipplllp",

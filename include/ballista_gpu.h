@@ -491,6 +491,55 @@ int bg_hashjoin_probe_mark2_filtered(void* handle, const bg_column* keys,
                                      const bg_join_filter_term* terms,
                                      int32_t nterms);
 
+/* ---- nested-loop join ----
+ * DataFusion 55 NestedLoopJoinExec (wire format: NestedLoopJoinExecNode,
+ * datafusion.proto:1359-1365; approved/q11.txt:69, q22.txt:14): a join
+ * without equi-keys, so EVERY (build row, probe row) pair is a candidate and
+ * the JoinFilter alone decides which pass.  Build = its left input, as in
+ * the hash joins; join types, "match = passing candidate", the visited
+ * bitmap and BG_JOIN_NULL_IDX read as in the bg_hashjoin_*2 family.  There
+ * are no keys and so no key-NULL rule: the only NULL rule is the filter's
+ * (a NULL on either side of a cross compare fails that term).
+ *
+ * PAIR ORDER is fixed: ascending probe row, and within a probe row ascending
+ * build row (SEMI emits the lowest passing build row).  An unmatched probe
+ * row (ANTI / OUTER_PROBE / OUTER_FULL) carries BG_JOIN_NULL_IDX.
+ *
+ * The handle holds no table, only the offsets between a count and its fill
+ * and one visited bit per build row (layout and lifetime of
+ * bg_hashjoin_build_rows2: lazily allocated by the first marking call,
+ * accumulated over every later one, bits at or beyond n_build never
+ * reported).  terms/nterms as in bg_hashjoin_probe_*2_filtered, with the
+ * same limits and messages, except that nterms == 0 is allowed here: every
+ * pair passes (CrossJoinExec).  The columns and masks the terms point at
+ * carry the rows; the calls take only the row counts.
+ *
+ * Work is n_build candidates per probe row and parallel over probe rows
+ * only: a one-row probe side against a large build side runs serially.
+ * DataFusion puts the smaller input on the build side.
+ *
+ * Every entry refuses with BG_ERR_INVALID, before anything is allocated or
+ * launched: a NULL handle (bg_nljoin_free(NULL) stays BG_OK), a negative
+ * row count, n_build >= 2^32 - 1 (build rows travel as u32, the last value
+ * is BG_JOIN_NULL_IDX), and, in count and fill, a join_type outside
+ * BG_JOIN_INNER .. BG_JOIN_OUTER_FULL, types 4 and 5 (no pairs: call
+ * bg_nljoin_mark, then bg_nljoin_build_rows) and a fill whose n_probe,
+ * join_type or terms differ from the last count's. */
+int bg_nljoin_open(int64_t n_build, void** out_handle);
+int bg_nljoin_count(void* handle, int64_t n_probe, int32_t join_type,
+                    const bg_join_filter_term* terms, int32_t nterms,
+                    int64_t* out_matches);
+int bg_nljoin_fill(void* handle, int64_t n_probe, int32_t join_type,
+                   const bg_join_filter_term* terms, int32_t nterms,
+                   uint32_t* d_out_probe, uint32_t* d_out_build);
+/* types 4/5 (and any chunk whose pairs are not wanted): mark only */
+int bg_nljoin_mark(void* handle, int64_t n_probe,
+                   const bg_join_filter_term* terms, int32_t nterms);
+/* as bg_hashjoin_build_rows2 */
+int bg_nljoin_build_rows(void* handle, int32_t matched, int64_t* out_count,
+                         uint32_t* d_out_build);
+int bg_nljoin_free(void* handle);
+
 /* Split an index vector carrying BG_JOIN_NULL_IDX sentinels (probe-outer
  * build side) into a clamped gather-safe vector + the validity bitmap of
  * non-sentinel slots. */

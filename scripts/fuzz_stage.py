@@ -3,7 +3,8 @@
 through random plan trees (filter -> optional hash join -> group-by
 aggregate [-> sort/limit]), every run checked against pyarrow compute.
 Covers the plan grammar end to end: expression eval, LIKE, join types with
-and without a residual filter, partial/final over a real shuffle file round trip (every 5th round).
+and without a residual filter, nested-loop joins (no keys) on all eight
+types, partial/final over a real shuffle file round trip (every 5th round).
 
 Usage: python scripts/fuzz_stage.py [rounds] [seed]"""
 import decimal
@@ -239,9 +240,58 @@ def run_round(ctx, rng, trial, tmpdir):
         want_n = n
     assert len(res3["rows"]) == want_n, (trial, jt, len(res3["rows"]),
                                          want_n)
+
+    # nested-loop join (no keys): a small build side (at most 64 rows)
+    # against the whole table under a random cross compare, any of the eight
+    # types, checked like the join above by its row count (counted on the
+    # device: an inner nested-loop join can emit nb * n rows)
+    njt = str(rng.choice(["inner", "semi", "anti", "left", "semi_build",
+                          "anti_build", "outer_build", "full"]))
+    nnb = int(rng.integers(1, 65))
+    nw = rng.integers(-10**8, 10**8, size=nnb, dtype=np.int64)
+    nwmask = rng.random(nnb) < 0.1
+    nt = pa.table({"bv": pa.array(np.arange(nnb, dtype=np.int64)),
+                   "bw": pa.array(nw, mask=nwmask)})
+    keep3 = stage.register_table(ctx, name + "n", nt)
+    build_only = njt in ("semi_build", "anti_build")
+    nj = {"op": "nested_loop_join",
+          "build": {"op": "scan", "schema": stage.schema_json(nt.schema),
+                    "source": {"kind": "device", "table": name + "n"}},
+          "probe": scan, "join_type": njt,
+          "output": [{"side": "build", "col": "bv"} if build_only
+                     else {"side": "probe", "col": "k"}]}
+    if rng.random() < 0.5:
+        nj["probe_chunk_rows"] = int(rng.integers(64, 4096))
+    v_ok = ~t["v"].is_null().to_numpy()
+    v_i = pc.fill_null(t["v"], 0).to_numpy()
+    passing = np.ones((nnb, n), dtype=bool)            # no filter: cross join
+    if rng.random() < 0.8:
+        cmp = str(rng.choice(["lt", "le", "gt", "ge", "eq", "ne"]))
+        groups = [{"cross": [{"build": "bw", "cmp": cmp, "probe": "v"}]}]
+        passing = (getattr(operator, cmp)(nw[:, None], v_i[None, :]) &
+                   ~nwmask[:, None] & v_ok[None, :])
+        if rng.random() < 0.5:      # OR a probe-side group
+            cut = int(rng.integers(8000, 11000))
+            groups.append({"probe": [{"col": "d", "cmp": "lt", "hi": cut}]})
+            passing = passing | (d_np < cut)[None, :]
+        nj["filter"] = {"any": groups}
+    pairs = int(passing.sum())
+    lone_probe = n - int(passing.any(axis=0).sum())
+    lone_build = nnb - int(passing.any(axis=1).sum())
+    want_n = {"inner": pairs, "semi": n - lone_probe, "anti": lone_probe,
+              "left": pairs + lone_probe, "semi_build": nnb - lone_build,
+              "anti_build": lone_build, "outer_build": pairs + lone_build,
+              "full": pairs + lone_probe + lone_build}[njt]
+    res4 = stage.execute(doc({"op": "collect", "input": {
+        "op": "hash_aggregate", "mode": "single", "group_by": [],
+        "aggs": [{"fn": "count", "as": "c"}], "input": nj}}))
+    got_n = res4["rows"][0][0] if res4["rows"] else 0
+    assert got_n == want_n, (trial, "nested_loop_join", njt, got_n, want_n)
+
     stage.unregister_table(name)
     stage.unregister_table(name + "b")
-    del keep, keep2
+    stage.unregister_table(name + "n")
+    del keep, keep2, keep3
 
 
 def main():
