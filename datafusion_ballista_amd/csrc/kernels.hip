@@ -9070,3 +9070,838 @@ extern "C" int bg_div_dec128(const bg_column* a, const bg_column* b,
   }
   return BG_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Window functions over sorted input (DataFusion's BoundedWindowAggExec /
+// WindowAggExec with InputOrderMode::Sorted; Ballista's
+// PartitionedBoundedWindowAggExec wraps the former).  The sort is upstream
+// (bg_sort_rows2); what runs here is the bandwidth-bound pass over sorted
+// rows: partition and peer-group heads as ballot bitmaps, ranks, prefix
+// arrays and frame lookups.
+//
+// Every device-wide scan is hierarchical in SEPARATE launches — per-span
+// aggregates, one block scanning the aggregates, a rescan with the carries
+// — and no workgroup ever waits for another inside a launch.  A span is
+// WIN_SPAN rows (a power of two <= 65536).  One scan kernel serves every
+// use: its operator works on (value, has, head) triples, so sums, running
+// extrema, restarts at partition heads and NULL inputs are one code path.
+// ---------------------------------------------------------------------------
+#define WIN_SPAN 4096
+#define WIN_OP_SUM 0
+#define WIN_OP_MIN 1
+#define WIN_OP_MAX 2
+#define WIN_HAS 1u   // the element carries a value (a non-NULL input so far)
+#define WIN_HEAD 2u  // the element starts a segment (or contains a start)
+
+template <class T>
+struct WinElem {
+  T v;
+  uint32_t fl;
+};
+
+// wrap-exact adds: Int64 and Decimal128 sums are arithmetic mod 2^64/2^128
+__device__ __forceinline__ i64 win_add(i64 a, i64 b) {
+  return (i64)((u64)a + (u64)b);
+}
+__device__ __forceinline__ i128 win_add(i128 a, i128 b) {
+  return (i128)((u128)a + (u128)b);
+}
+__device__ __forceinline__ double win_add(double a, double b) { return a + b; }
+__device__ __forceinline__ i64 win_sub(i64 a, i64 b) {
+  return (i64)((u64)a - (u64)b);
+}
+__device__ __forceinline__ i128 win_sub(i128 a, i128 b) {
+  return (i128)((u128)a - (u128)b);
+}
+__device__ __forceinline__ double win_sub(double a, double b) { return a - b; }
+
+template <class T>
+__device__ __forceinline__ T win_op(int op, T a, T b) {
+  if (op == WIN_OP_SUM) return win_add(a, b);
+  if (op == WIN_OP_MIN) return b < a ? b : a;
+  return b > a ? b : a;
+}
+
+// the segmented-scan operator: a head on the right discards the left
+template <class T>
+__device__ __forceinline__ WinElem<T> win_combine(int op, const WinElem<T>& a,
+                                                  const WinElem<T>& b) {
+  if (b.fl & WIN_HEAD) return b;
+  WinElem<T> r;
+  r.fl = a.fl | b.fl;
+  r.v = (a.fl & b.fl & WIN_HAS) ? win_op(op, a.v, b.v)
+                                : ((b.fl & WIN_HAS) ? b.v : a.v);
+  return r;
+}
+
+__device__ __forceinline__ i64 win_shfl_up(i64 v, int d) {
+  return __shfl_up(v, d, BG_WAVE);
+}
+__device__ __forceinline__ double win_shfl_up(double v, int d) {
+  return __shfl_up(v, d, BG_WAVE);
+}
+__device__ __forceinline__ i128 win_shfl_up(i128 v, int d) {
+  const i64 lo = __shfl_up((i64)(u64)(u128)v, d, BG_WAVE);
+  const i64 hi = __shfl_up((i64)(u64)((u128)v >> 64), d, BG_WAVE);
+  return make_i128((u64)lo, hi);
+}
+
+// IEEE total order as a signed i64 (its own inverse): the order of
+// k_key_transform_f64 and BG_AGG_OP_MIN_F64
+__device__ __forceinline__ i64 win_f64_key(i64 bits) {
+  return bits ^ ((bits >> 63) & 0x7FFFFFFFFFFFFFFFll);
+}
+
+// a value column as a scan reads it
+struct WinSrc {
+  const void* data;
+  const uint8_t* valid;
+  int dtype;  // BG_DT_*; FLOAT64 read as i64 is its total-order key
+};
+
+template <class T>
+__device__ __forceinline__ T win_load(const WinSrc& s, int64_t i);
+template <>
+__device__ __forceinline__ i64 win_load<i64>(const WinSrc& s, int64_t i) {
+  switch (s.dtype) {
+    case BG_DT_INT32:
+    case BG_DT_DATE32:
+      return (i64) reinterpret_cast<const int32_t*>(s.data)[i];
+    case BG_DT_FLOAT64:
+      return win_f64_key(reinterpret_cast<const i64*>(s.data)[i]);
+    default:
+      return reinterpret_cast<const i64*>(s.data)[i];
+  }
+}
+template <>
+__device__ __forceinline__ double win_load<double>(const WinSrc& s,
+                                                   int64_t i) {
+  return reinterpret_cast<const double*>(s.data)[i];
+}
+template <>
+__device__ __forceinline__ i128 win_load<i128>(const WinSrc& s, int64_t i) {
+  return load_dec128(s.data, i);
+}
+
+template <class T>
+struct WinScanArgs {
+  WinSrc src;                  // column mode (elems == NULL)
+  WinElem<T>* elems;           // element mode: scanned in place
+  const uint32_t* part_start;  // row i heads a segment iff part_start[i] == i
+  int op;
+  int64_t n;
+  WinElem<T>* blk;          // aggregate phase: one total per span, no writes
+  const WinElem<T>* carry;  // write phase: inclusive-scanned span totals
+  T* out;                   // write phase, column mode: inclusive prefix
+  u64* has_words;           // optional ballot of WIN_HAS per row
+};
+
+// One block walks a span in 256-row tiles: wave scan by shuffles, the four
+// wave totals through LDS (two buffers, so one barrier per tile), a running
+// carry in registers.
+template <class T>
+__global__ void __launch_bounds__(BG_BLOCK)
+    k_win_scan(WinScanArgs<T> a, int64_t nspans, int64_t span) {
+  constexpr int NW = BG_BLOCK / BG_WAVE;
+  __shared__ WinElem<T> wtot[2][NW];
+  const int lane = lane_id(), wv = threadIdx.x / BG_WAVE;
+  int par = 0;  // never reset: consecutive tiles alternate across spans too
+  for (int64_t sp = blockIdx.x; sp < nspans; sp += gridDim.x) {
+    WinElem<T> run;
+    run.v = (T)0;
+    run.fl = 0;
+    if (a.carry && sp > 0) run = a.carry[sp - 1];
+    const int64_t s0 = sp * span;
+    const int64_t s1 = s0 + span < a.n ? s0 + span : a.n;
+    for (int64_t base = s0; base < s1; base += BG_BLOCK, par ^= 1) {
+      const int64_t i = base + threadIdx.x;
+      WinElem<T> x;
+      x.v = (T)0;
+      x.fl = 0;
+      if (i < s1) {
+        if (a.elems) {
+          x = a.elems[i];
+        } else {
+          if (bit_valid(a.src.valid, i)) {
+            x.v = win_load<T>(a.src, i);
+            x.fl = WIN_HAS;
+          }
+          if (a.part_start && a.part_start[i] == (uint32_t)i)
+            x.fl |= WIN_HEAD;
+        }
+      }
+#pragma unroll
+      for (int d = 1; d < BG_WAVE; d <<= 1) {
+        WinElem<T> o;
+        o.v = win_shfl_up(x.v, d);
+        o.fl = __shfl_up(x.fl, d, BG_WAVE);
+        if (lane >= d) x = win_combine(a.op, o, x);
+      }
+      if (lane == BG_WAVE - 1) wtot[par][wv] = x;
+      __syncthreads();
+      WinElem<T> acc = run, mine = run;
+#pragma unroll
+      for (int k = 0; k < NW; ++k) {
+        if (k == wv) mine = acc;
+        acc = win_combine(a.op, acc, wtot[par][k]);
+      }
+      x = win_combine(a.op, mine, x);
+      run = acc;
+      if (a.blk == nullptr) {
+        if (i < s1) {
+          if (a.elems) a.elems[i] = x;
+          else a.out[i] = x.v;
+        }
+        if (a.has_words) {
+          const u64 m = __ballot(i < s1 && (x.fl & WIN_HAS));
+          const int64_t w0 = base + (int64_t)wv * BG_WAVE;
+          if (lane == 0 && w0 < s1) a.has_words[w0 >> 6] = m;
+        }
+      }
+    }
+    if (a.blk && threadIdx.x == 0) a.blk[sp] = run;
+  }
+}
+
+// Inclusive (optionally segmented) scan of a column: out[i] = the running
+// op over the rows of i's segment up to i, NULL inputs skipped.
+template <class T>
+static int win_scan(const WinSrc& src, const uint32_t* d_part_start, int op,
+                    int64_t n, T* d_out, u64* d_has_words) {
+  const int64_t nsp = (n + WIN_SPAN - 1) / WIN_SPAN;
+  DevBuf<WinElem<T>> d_blk;
+  WinScanArgs<T> a{};
+  a.src = src;
+  a.part_start = d_part_start;
+  a.op = op;
+  a.n = n;
+  const int blocks = (int)bg_imin64(nsp, BG_MAX_BLOCKS);
+  if (nsp > 1) {
+    HIP_TRY(d_blk.alloc(nsp));
+    a.blk = d_blk;
+    hipLaunchKernelGGL(k_win_scan<T>, dim3(blocks), dim3(BG_BLOCK), 0, 0, a,
+                       nsp, (int64_t)WIN_SPAN);
+    WinScanArgs<T> c{};
+    c.elems = d_blk;
+    c.op = op;
+    c.n = nsp;
+    hipLaunchKernelGGL(k_win_scan<T>, dim3(1), dim3(BG_BLOCK), 0, 0, c,
+                       (int64_t)1, nsp);
+    a.carry = d_blk;
+  }
+  a.blk = nullptr;
+  a.out = d_out;
+  a.has_words = d_has_words;
+  hipLaunchKernelGGL(k_win_scan<T>, dim3(blocks), dim3(BG_BLOCK), 0, 0, a, nsp,
+                     (int64_t)WIN_SPAN);
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+// ---- head bitmaps and the [start, end) arrays they imply ----
+
+// One thread per row compares row i with row i-1; a wave's 64 verdicts
+// leave as one ballot word, so both head sets are Arrow bitmaps.
+__global__ void k_win_heads(KeyArgs part, KeyArgs order, int64_t n,
+                            u64* part_words, u64* peer_words,
+                            int64_t nwords) {
+  const int64_t wave_global =
+      ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / BG_WAVE;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) / BG_WAVE;
+  for (int64_t w = wave_global; w < nwords; w += nwaves) {
+    const int64_t row = w * BG_WAVE + lane_id();
+    bool ph = false, qh = false;
+    if (row < n) {
+      ph = row == 0 || !keys_equal_rows(part, row - 1, row);
+      qh = ph || !keys_equal_rows(order, row - 1, row);
+    }
+    const u64 pm = __ballot(ph), qm = __ballot(qh);
+    if (lane_id() == 0) {
+      part_words[w] = pm;
+      peer_words[w] = qm;
+    }
+  }
+}
+
+// Per word: its last set bit's row (-1: none) for the forward max scan, and
+// minus its first set bit's row (-n: none), stored in reverse word order,
+// so the backward min scan is a forward max scan too.
+__global__ void k_win_word_edges(const u64* words, int64_t nwords, int64_t n,
+                                 i64* fwd, i64* bwd) {
+  for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < nwords;
+       w += (int64_t)gridDim.x * blockDim.x) {
+    const u64 m = words[w];
+    fwd[w] = m ? w * 64 + 63 - __clzll((long long)m) : -1;
+    bwd[nwords - 1 - w] = m ? -(w * 64 + (__ffsll((long long)m) - 1)) : -n;
+  }
+}
+
+// start[i] = the previous set bit at or before i, end[i] = the next set bit
+// after i (or n): inside the word by clz/ctz on the masked word, across
+// words from the two scanned carry arrays.  Every result is clamped, so no
+// input can produce an index outside [0, n].
+__global__ void k_win_bounds_fill(const u64* words, const i64* fwd_scan,
+                                  const i64* bwd_scan, int64_t nwords,
+                                  int64_t n, uint32_t* start_out,
+                                  uint32_t* end_out) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t w = i >> 6;
+    const int l = (int)(i & 63);
+    const u64 m = words[w];
+    if (start_out) {
+      const u64 le = m & (~0ull >> (63 - l));
+      int64_t s = le ? w * 64 + 63 - __clzll((long long)le)
+                     : (w > 0 ? fwd_scan[w - 1] : 0);
+      if (s < 0) s = 0;
+      if (s > i) s = i;
+      start_out[i] = (uint32_t)s;
+    }
+    if (end_out) {
+      const u64 gt = l == 63 ? 0ull : m & (~0ull << (l + 1));
+      int64_t e = gt ? w * 64 + (__ffsll((long long)gt) - 1)
+                     : (w + 1 < nwords ? -bwd_scan[nwords - 2 - w] : n);
+      if (e <= i) e = i + 1;
+      if (e > n) e = n;
+      end_out[i] = (uint32_t)e;
+    }
+  }
+}
+
+static void win_key_args(const bg_column* cols, int32_t ncols, KeyArgs* a) {
+  a->nkeys = ncols;
+  for (int i = 0; i < ncols; ++i) {
+    a->k[i].data = cols[i].d_data;
+    a->k[i].valid = cols[i].d_validity;
+    a->k[i].offsets = cols[i].d_offsets;
+    // Float64 keys compare by bit pattern: -0.0 and +0.0 differ, equal NaN
+    // patterns match (k_key_transform_f64's total order)
+    a->k[i].dtype =
+        cols[i].dtype == BG_DT_FLOAT64 ? (int)BG_DT_INT64 : cols[i].dtype;
+  }
+}
+
+static int win_check_n(const char* who, int64_t n) {
+  if (n < 0 || n > (int64_t)UINT32_MAX - 1) {
+    char msg[96];
+    snprintf(msg, sizeof(msg), "%s: n outside [0, 2^32 - 2]", who);
+    return set_err(BG_ERR_INVALID, msg);
+  }
+  return BG_OK;
+}
+
+// start/end arrays of one head bitmap; either output may be NULL
+static int win_bounds_of(const u64* d_words, int64_t nwords, int64_t n,
+                         i64* d_fwd, i64* d_bwd, i64* d_fscan, i64* d_bscan,
+                         uint32_t* d_start, uint32_t* d_end) {
+  if (!d_start && !d_end) return BG_OK;
+  hipLaunchKernelGGL(k_win_word_edges, dim3(grid_for(nwords)), dim3(BG_BLOCK),
+                     0, 0, d_words, nwords, n, d_fwd, d_bwd);
+  const WinSrc f{d_fwd, nullptr, BG_DT_INT64}, b{d_bwd, nullptr, BG_DT_INT64};
+  int rc = win_scan<i64>(f, nullptr, WIN_OP_MAX, nwords, d_fscan, nullptr);
+  if (rc != BG_OK) return rc;
+  rc = win_scan<i64>(b, nullptr, WIN_OP_MAX, nwords, d_bscan, nullptr);
+  if (rc != BG_OK) return rc;
+  hipLaunchKernelGGL(k_win_bounds_fill, dim3(grid_for(n)), dim3(BG_BLOCK), 0,
+                     0, d_words, d_fscan, d_bscan, nwords, n, d_start, d_end);
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+extern "C" int bg_window_bounds(const bg_column* part_cols, int32_t npart,
+                                const bg_column* order_cols, int32_t norder,
+                                int64_t n, uint32_t* d_part_start,
+                                uint32_t* d_part_end, uint32_t* d_peer_start,
+                                uint32_t* d_peer_end) {
+  REQUIRE_INIT();
+  if (npart < 0 || npart > BG_MAX_KEYS || norder < 0 || norder > BG_MAX_KEYS)
+    return set_err(BG_ERR_INVALID,
+                   "bg_window_bounds: 0-4 partition and 0-4 order columns");
+  if ((npart > 0 && !part_cols) || (norder > 0 && !order_cols))
+    return set_err(BG_ERR_INVALID, "bg_window_bounds: NULL key columns");
+  if (int rc = win_check_n("bg_window_bounds", n)) return rc;
+  if (n == 0) return BG_OK;
+  KeyArgs pk{}, ok{};
+  win_key_args(part_cols, npart, &pk);
+  win_key_args(order_cols, norder, &ok);
+  const int64_t nwords = (n + 63) / 64;
+  DevBuf<u64> d_part_words, d_peer_words;
+  DevBuf<i64> d_fwd, d_bwd, d_fscan, d_bscan;
+  HIP_TRY(d_part_words.alloc(nwords));
+  HIP_TRY(d_peer_words.alloc(nwords));
+  HIP_TRY(d_fwd.alloc(nwords));
+  HIP_TRY(d_bwd.alloc(nwords));
+  HIP_TRY(d_fscan.alloc(nwords));
+  HIP_TRY(d_bscan.alloc(nwords));
+  hipLaunchKernelGGL(k_win_heads, dim3(grid_for(n)), dim3(BG_BLOCK), 0, 0, pk,
+                     ok, n, d_part_words.get(), d_peer_words.get(), nwords);
+  HIP_TRY(hipGetLastError());
+  int rc = win_bounds_of(d_part_words, nwords, n, d_fwd, d_bwd, d_fscan,
+                         d_bscan, d_part_start, d_part_end);
+  if (rc != BG_OK) return rc;
+  return win_bounds_of(d_peer_words, nwords, n, d_fwd, d_bwd, d_fscan, d_bscan,
+                       d_peer_start, d_peer_end);
+}
+
+// ---- counting prefixes over a bitmap ----
+
+// A row set as ballot words plus their popcounts: a validity bitmap read
+// bit by bit (so no byte past ceil(n/8) is touched), or the rows that head
+// their own group (self[i] == i).
+__global__ void k_win_flag_words(const uint8_t* valid, const uint32_t* self,
+                                 int64_t n, u64* words, uint32_t* pops,
+                                 int64_t nwords) {
+  const int64_t wave_global =
+      ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / BG_WAVE;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) / BG_WAVE;
+  for (int64_t w = wave_global; w < nwords; w += nwaves) {
+    const int64_t row = w * BG_WAVE + lane_id();
+    bool f = false;
+    if (row < n) f = valid ? bit_valid(valid, row) : self[row] == (uint32_t)row;
+    const u64 m = __ballot(f);
+    if (lane_id() == 0) {
+      words[w] = m;
+      pops[w] = (uint32_t)__popcll(m);
+    }
+  }
+}
+
+// words == NULL: every row is in the set
+struct WinCnt {
+  const u64* words;
+  const i64* pre;  // exclusive prefix of the words' popcounts
+};
+
+// members of the set among rows [0, j]
+__device__ __forceinline__ int64_t win_cnt_incl(const WinCnt& c, int64_t j) {
+  if (!c.words) return j + 1;
+  return c.pre[j >> 6] +
+         __popcll(c.words[j >> 6] & (~0ull >> (63 - (int)(j & 63))));
+}
+
+struct WinCntBufs {
+  DevBuf<u64> words;
+  DevBuf<uint32_t> pops;
+  DevBuf<i64> pre;
+};
+
+static int win_count_prefix(const uint8_t* d_valid, const uint32_t* d_self,
+                            int64_t n, WinCntBufs* b, WinCnt* out) {
+  const int64_t nwords = (n + 63) / 64;
+  HIP_TRY(b->words.alloc(nwords));
+  HIP_TRY(b->pops.alloc(nwords));
+  HIP_TRY(b->pre.alloc(nwords));
+  hipLaunchKernelGGL(k_win_flag_words, dim3(grid_for(n)), dim3(BG_BLOCK), 0, 0,
+                     d_valid, d_self, n, b->words.get(), b->pops.get(), nwords);
+  HIP_TRY(hipGetLastError());
+  if (int rc = scan_exclusive_u32(b->pops, nwords, b->pre, nullptr)) return rc;
+  out->words = b->words;
+  out->pre = b->pre;
+  return BG_OK;
+}
+
+// ---- ranking ----
+
+__global__ void k_win_rank(int32_t fn, const uint32_t* part_start,
+                           const uint32_t* peer_start, WinCnt heads, int64_t n,
+                           int64_t* out) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t ps = part_start ? (int64_t)part_start[i] : 0;
+    if (ps > i) ps = i;
+    int64_t r;
+    if (fn == BG_WIN_ROW_NUMBER) {
+      r = i - ps + 1;
+    } else if (fn == BG_WIN_RANK) {
+      int64_t q = peer_start[i];
+      if (q > i) q = i;
+      if (q < ps) q = ps;
+      r = q - ps + 1;
+    } else {  // peer-group heads in (ps, i], plus the partition's own
+      r = win_cnt_incl(heads, i) - win_cnt_incl(heads, ps) + 1;
+    }
+    out[i] = r;
+  }
+}
+
+extern "C" int bg_window_rank(int32_t fn, const uint32_t* d_part_start,
+                              const uint32_t* d_peer_start, int64_t n,
+                              int64_t* d_out) {
+  REQUIRE_INIT();
+  if (fn != BG_WIN_ROW_NUMBER && fn != BG_WIN_RANK && fn != BG_WIN_DENSE_RANK)
+    return set_err(BG_ERR_INVALID, "bg_window_rank: unknown fn");
+  if (int rc = win_check_n("bg_window_rank", n)) return rc;
+  if (n == 0) return BG_OK;
+  if (!d_out || (fn != BG_WIN_ROW_NUMBER && !d_peer_start))
+    return set_err(BG_ERR_INVALID,
+                   "bg_window_rank: NULL output or peer starts");
+  WinCntBufs bufs;
+  WinCnt heads{nullptr, nullptr};
+  if (fn == BG_WIN_DENSE_RANK)
+    if (int rc = win_count_prefix(nullptr, d_peer_start, n, &bufs, &heads))
+      return rc;
+  hipLaunchKernelGGL(k_win_rank, dim3(grid_for(n)), dim3(BG_BLOCK), 0, 0, fn,
+                     d_part_start, d_peer_start, heads, n, d_out);
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+// ---- frames ----
+
+struct WinFrameArgs {
+  int units, start_kind, end_kind, descending;
+  int64_t start_off, end_off;  // i64, or f64 bits for a FLOAT64 range key
+  WinSrc key;                  // data == NULL: no RANGE offset bound
+  const uint32_t *part_start, *part_end, *peer_start, *peer_end;
+  int64_t n;
+  uint32_t *lo, *hi;
+};
+
+// First row of [a, b) whose key is at or after t in the sort direction
+// (strict: after t).  The step count is bounded: b - a < 2^32.
+template <class K>
+__device__ __forceinline__ int64_t win_search(const WinSrc& key, int64_t a,
+                                              int64_t b, K t, bool desc,
+                                              bool strict) {
+  int64_t l = a, r = b;
+  for (int it = 0; it < 33 && l < r; ++it) {
+    const int64_t m = l + ((r - l) >> 1);
+    const K k = win_load<K>(key, m);
+    const bool p = strict ? (desc ? k < t : k > t) : (desc ? k <= t : k >= t);
+    if (p) r = m;
+    else l = m + 1;
+  }
+  return l;
+}
+
+__device__ __forceinline__ i64 win_sat_add(i64 a, i64 b) {
+  i64 r;
+  if (__builtin_add_overflow(a, b, &r))
+    return b < 0 ? (i64)0x8000000000000000ull : 0x7FFFFFFFFFFFFFFFll;
+  return r;
+}
+
+// the row a RANGE offset bound resolves to; delta is the signed offset
+// along the sort direction (preceding < 0 < following)
+__device__ __forceinline__ int64_t win_range_bound(const WinFrameArgs& f,
+                                                   int64_t i, int64_t a,
+                                                   int64_t b, bool following,
+                                                   int64_t off, bool is_end) {
+  if (f.key.dtype == BG_DT_FLOAT64) {
+    double x;
+    __builtin_memcpy(&x, &off, 8);
+    const double d = following ? x : -x;
+    const double k = win_load<double>(f.key, i);
+    return win_search<double>(f.key, a, b, f.descending ? k - d : k + d,
+                              f.descending != 0, is_end);
+  }
+  const i64 d = following ? off : -off;
+  const i64 k = win_load<i64>(f.key, i);
+  return win_search<i64>(f.key, a, b,
+                         f.descending ? win_sat_add(k, -d) : win_sat_add(k, d),
+                         f.descending != 0, is_end);
+}
+
+__global__ void k_win_frame(WinFrameArgs f) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < f.n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    // partition and peer group of row i, forced to ps <= qs <= i < qe <= pe
+    int64_t ps = f.part_start[i], pe = f.part_end[i];
+    if (ps > i) ps = i;
+    if (pe <= i) pe = i + 1;
+    if (pe > f.n) pe = f.n;
+    int64_t lo, hi;
+    if (f.units == BG_WIN_ROWS) {
+      const int64_t so = f.start_off < f.n ? f.start_off : f.n;
+      const int64_t eo = f.end_off < f.n ? f.end_off : f.n;
+      lo = f.start_kind == BG_WIN_UNBOUNDED     ? ps
+           : f.start_kind == BG_WIN_CURRENT_ROW ? i
+           : f.start_kind == BG_WIN_PRECEDING   ? i - so
+                                                : i + so;
+      hi = f.end_kind == BG_WIN_UNBOUNDED     ? pe
+           : f.end_kind == BG_WIN_CURRENT_ROW ? i + 1
+           : f.end_kind == BG_WIN_FOLLOWING   ? i + eo + 1
+                                              : i - eo + 1;
+    } else {
+      int64_t qs = f.peer_start[i], qe = f.peer_end[i];
+      if (qs > i) qs = i;
+      if (qs < ps) qs = ps;
+      if (qe <= i) qe = i + 1;
+      if (qe > pe) qe = pe;
+      const bool s_off = f.start_kind >= BG_WIN_PRECEDING;
+      const bool e_off = f.end_kind >= BG_WIN_PRECEDING;
+      lo = f.start_kind == BG_WIN_UNBOUNDED ? ps : qs;
+      hi = f.end_kind == BG_WIN_UNBOUNDED ? pe : qe;
+      // a NULL key keeps its NULL peer group as the offset side
+      if ((s_off || e_off) && bit_valid(f.key.valid, i)) {
+        // the partition's non-NULL rows [a, b): its NULLs are one peer
+        // group at one end
+        int64_t a = ps, b = pe;
+        if (f.key.valid) {
+          if (!bit_valid(f.key.valid, ps)) {
+            a = f.peer_end[ps];
+            if (a <= ps) a = ps + 1;
+            if (a > pe) a = pe;
+          } else if (!bit_valid(f.key.valid, pe - 1)) {
+            b = f.peer_start[pe - 1];
+            if (b > pe - 1) b = pe - 1;
+            if (b < ps) b = ps;
+          }
+        }
+        if (s_off)
+          lo = win_range_bound(f, i, a, b, f.start_kind == BG_WIN_FOLLOWING,
+                               f.start_off, false);
+        if (e_off)
+          hi = win_range_bound(f, i, a, b, f.end_kind == BG_WIN_FOLLOWING,
+                               f.end_off, true);
+      }
+    }
+    if (lo < ps) lo = ps;
+    if (lo > pe) lo = pe;
+    if (hi > pe) hi = pe;
+    if (hi < lo) hi = lo;
+    f.lo[i] = (uint32_t)lo;
+    f.hi[i] = (uint32_t)hi;
+  }
+}
+
+extern "C" int bg_window_frame(int32_t units, int32_t start_kind,
+                               int64_t start_off, int32_t end_kind,
+                               int64_t end_off, const bg_column* order_col,
+                               int32_t descending,
+                               const uint32_t* d_part_start,
+                               const uint32_t* d_part_end,
+                               const uint32_t* d_peer_start,
+                               const uint32_t* d_peer_end, int64_t n,
+                               uint32_t* d_lo, uint32_t* d_hi) {
+  REQUIRE_INIT();
+  if (units != BG_WIN_ROWS && units != BG_WIN_RANGE)
+    return set_err(BG_ERR_UNSUPPORTED,
+                   "bg_window_frame: units must be ROWS or RANGE");
+  auto kind_ok = [](int32_t k) {
+    return k >= BG_WIN_UNBOUNDED && k <= BG_WIN_FOLLOWING;
+  };
+  if (!kind_ok(start_kind) || !kind_ok(end_kind))
+    return set_err(BG_ERR_INVALID, "bg_window_frame: unknown bound kind");
+  const bool s_off = start_kind >= BG_WIN_PRECEDING;
+  const bool e_off = end_kind >= BG_WIN_PRECEDING;
+  const bool range_off = units == BG_WIN_RANGE && (s_off || e_off);
+  const bool f64 = range_off && order_col && order_col->dtype == BG_DT_FLOAT64;
+  auto off_ok = [f64](int64_t off) {
+    if (!f64) return off >= 0;
+    double x;
+    memcpy(&x, &off, 8);
+    return x >= 0.0;  // false for NaN as well
+  };
+  if ((s_off && !off_ok(start_off)) || (e_off && !off_ok(end_off)))
+    return set_err(BG_ERR_INVALID, "bg_window_frame: negative offset");
+  if (range_off) {
+    if (!order_col)
+      return set_err(BG_ERR_INVALID,
+                     "bg_window_frame: a RANGE offset needs the order column");
+    const int32_t dt = order_col->dtype;
+    if (dt != BG_DT_INT64 && dt != BG_DT_INT32 && dt != BG_DT_DATE32 &&
+        dt != BG_DT_FLOAT64)
+      return set_err(BG_ERR_UNSUPPORTED,
+                     "bg_window_frame: RANGE offset over a key that is not "
+                     "Int64/Int32/Date32/Float64");
+  }
+  if (int rc = win_check_n("bg_window_frame", n)) return rc;
+  if (n == 0) return BG_OK;
+  if (!d_part_start || !d_part_end || !d_lo || !d_hi ||
+      (units == BG_WIN_RANGE && (!d_peer_start || !d_peer_end)))
+    return set_err(BG_ERR_INVALID, "bg_window_frame: NULL bounds array");
+  WinFrameArgs f{};
+  f.units = units;
+  f.start_kind = start_kind;
+  f.end_kind = end_kind;
+  f.descending = descending ? 1 : 0;
+  f.start_off = s_off ? start_off : 0;
+  f.end_off = e_off ? end_off : 0;
+  if (range_off)
+    f.key = WinSrc{order_col->d_data, order_col->d_validity, order_col->dtype};
+  f.part_start = d_part_start;
+  f.part_end = d_part_end;
+  f.peer_start = d_peer_start;
+  f.peer_end = d_peer_end;
+  f.n = n;
+  f.lo = d_lo;
+  f.hi = d_hi;
+  hipLaunchKernelGGL(k_win_frame, dim3(grid_for(n)), dim3(BG_BLOCK), 0, 0, f);
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+// ---- aggregates over a frame ----
+
+template <class T>
+struct WinFinishArgs {
+  int fn;             // BG_WIN_SUM / COUNT / MIN / MAX
+  int out_dtype;      // how a value leaves: BG_DT_*
+  int seg;            // the prefix restarts at every partition start
+  const T* prefix;    // inclusive prefix / running extremum (NULL: count)
+  const u64* has_words;  // MIN/MAX: rows whose running extremum exists
+  WinCnt cnt;            // non-NULL inputs
+  const uint32_t *part_start, *lo, *hi;
+  int64_t n;
+  void* out;
+  uint8_t* valid_out;
+};
+
+__device__ __forceinline__ void win_store(void* out, int dt, int64_t i,
+                                          i64 v) {
+  if (dt == BG_DT_INT32 || dt == BG_DT_DATE32)
+    reinterpret_cast<int32_t*>(out)[i] = (int32_t)v;
+  else if (dt == BG_DT_FLOAT64)  // a total-order key back to its bits
+    reinterpret_cast<i64*>(out)[i] = win_f64_key(v);
+  else
+    reinterpret_cast<i64*>(out)[i] = v;
+}
+__device__ __forceinline__ void win_store(void* out, int, int64_t i,
+                                          double v) {
+  reinterpret_cast<double*>(out)[i] = v;
+}
+__device__ __forceinline__ void win_store(void* out, int, int64_t i, i128 v) {
+  ulong2 o;
+  o.x = (u64)(u128)v;
+  o.y = (u64)((u128)v >> 64);
+  reinterpret_cast<ulong2*>(out)[i] = o;
+}
+
+// One thread per row reads the prefix at its frame's two ends.  Whole waves
+// iterate, so a wave's 64 validity verdicts are one ballot and eight lanes
+// store its bytes: ceil(n/8) bytes written whole, none beyond.
+template <class T>
+__global__ void k_win_agg_finish(WinFinishArgs<T> a, int64_t nwords) {
+  const int64_t wave_global =
+      ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / BG_WAVE;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) / BG_WAVE;
+  const int64_t nbytes = (a.n + 7) / 8;
+  for (int64_t w = wave_global; w < nwords; w += nwaves) {
+    const int64_t i = w * BG_WAVE + lane_id();
+    bool ok = false;
+    if (i < a.n) {
+      int64_t ps = a.part_start ? (int64_t)a.part_start[i] : 0;
+      if (ps > i) ps = i;
+      int64_t lo = a.lo ? (int64_t)a.lo[i] : ps;
+      int64_t hi = a.hi[i];
+      if (lo > a.n) lo = a.n;
+      if (hi > a.n) hi = a.n;
+      if (hi < lo) hi = lo;
+      if (a.fn == BG_WIN_COUNT || a.fn == BG_WIN_SUM) {
+        int64_t c = 0;
+        if (hi > lo)
+          c = win_cnt_incl(a.cnt, hi - 1) -
+              (lo > 0 ? win_cnt_incl(a.cnt, lo - 1) : 0);
+        ok = c > 0;
+        if (a.fn == BG_WIN_COUNT) {
+          reinterpret_cast<i64*>(a.out)[i] = c;
+        } else {
+          T s = (T)0;
+          if (ok) {
+            s = a.prefix[hi - 1];
+            if (lo > (a.seg ? ps : 0)) s = win_sub(s, a.prefix[lo - 1]);
+          }
+          win_store(a.out, a.out_dtype, i, s);
+        }
+      } else {
+        ok = hi > lo && ((a.has_words[(hi - 1) >> 6] >> ((hi - 1) & 63)) & 1);
+        win_store(a.out, a.out_dtype, i, ok ? a.prefix[hi - 1] : (T)0);
+      }
+    }
+    const u64 m = __ballot(ok);
+    if (a.valid_out && lane_id() < 8 && w * 8 + lane_id() < nbytes)
+      a.valid_out[w * 8 + lane_id()] = (uint8_t)(m >> (8 * lane_id()));
+  }
+}
+
+// prefix (and, for MIN/MAX, the has bitmap) of val, then the per-row pass
+template <class T>
+static int win_agg_run(int32_t fn, const bg_column* val, int seg,
+                       const WinCnt& cnt, const uint32_t* d_part_start,
+                       const uint32_t* d_lo, const uint32_t* d_hi, int64_t n,
+                       void* d_out, uint8_t* d_valid_out) {
+  const int64_t nwords = (n + 63) / 64;
+  const bool extremum = fn == BG_WIN_MIN || fn == BG_WIN_MAX;
+  DevBuf<T> d_prefix;
+  DevBuf<u64> d_has;
+  WinFinishArgs<T> a{};
+  a.fn = fn;
+  a.seg = seg;
+  a.cnt = cnt;
+  a.part_start = d_part_start;
+  a.lo = d_lo;
+  a.hi = d_hi;
+  a.n = n;
+  a.out = d_out;
+  a.valid_out = d_valid_out;
+  if (fn != BG_WIN_COUNT) {
+    HIP_TRY(d_prefix.alloc(n));
+    if (extremum) HIP_TRY(d_has.alloc(nwords));
+    const WinSrc src{val->d_data, val->d_validity, val->dtype};
+    const int op = fn == BG_WIN_SUM   ? WIN_OP_SUM
+                   : fn == BG_WIN_MIN ? WIN_OP_MIN
+                                      : WIN_OP_MAX;
+    if (int rc = win_scan<T>(src, seg ? d_part_start : nullptr, op, n,
+                             d_prefix.get(), extremum ? d_has.get() : nullptr))
+      return rc;
+    a.prefix = d_prefix;
+    a.has_words = d_has;
+    a.out_dtype = val->dtype;
+  }
+  hipLaunchKernelGGL(k_win_agg_finish<T>, dim3(grid_for(n)), dim3(BG_BLOCK), 0,
+                     0, a, nwords);
+  HIP_TRY(hipGetLastError());
+  return BG_OK;
+}
+
+extern "C" int bg_window_agg(int32_t fn, const bg_column* val,
+                             const uint32_t* d_part_start,
+                             const uint32_t* d_lo, const uint32_t* d_hi,
+                             int64_t n, void* d_out, uint8_t* d_valid_out) {
+  REQUIRE_INIT();
+  if (fn < BG_WIN_SUM || fn > BG_WIN_MAX)
+    return set_err(BG_ERR_INVALID, "bg_window_agg: unknown fn");
+  const bool extremum = fn == BG_WIN_MIN || fn == BG_WIN_MAX;
+  if (extremum && d_lo)
+    return set_err(BG_ERR_UNSUPPORTED,
+                   "bg_window_agg: MIN/MAX only over frames that start at the "
+                   "partition start (d_lo must be NULL); a sliding extremum "
+                   "is not implemented");
+  if (!val && fn != BG_WIN_COUNT)
+    return set_err(BG_ERR_INVALID, "bg_window_agg: val is NULL (count only)");
+  const int32_t dt = val ? val->dtype : (int32_t)BG_DT_INT64;
+  if (fn == BG_WIN_SUM && dt != BG_DT_INT64 && dt != BG_DT_DECIMAL128 &&
+      dt != BG_DT_FLOAT64)
+    return set_err(BG_ERR_UNSUPPORTED,
+                   "bg_window_agg: SUM over Int64/Decimal128/Float64 only");
+  if (extremum && dt != BG_DT_INT64 && dt != BG_DT_INT32 &&
+      dt != BG_DT_DATE32 && dt != BG_DT_FLOAT64 && dt != BG_DT_DECIMAL128)
+    return set_err(BG_ERR_UNSUPPORTED,
+                   "bg_window_agg: MIN/MAX over Int64/Int32/Date32/Float64/"
+                   "Decimal128 only");
+  if (int rc = win_check_n("bg_window_agg", n)) return rc;
+  if (n == 0) return BG_OK;
+  if (!d_hi || !d_out || (!d_lo && !d_part_start) ||
+      (fn != BG_WIN_COUNT && !d_valid_out))
+    return set_err(BG_ERR_INVALID, "bg_window_agg: NULL array");
+  // non-NULL inputs per frame: a prefix only when the column has a bitmap
+  WinCntBufs bufs;
+  WinCnt cnt{nullptr, nullptr};
+  if (!extremum && val && val->d_validity)
+    if (int rc = win_count_prefix(val->d_validity, nullptr, n, &bufs, &cnt))
+      return rc;
+  if (fn == BG_WIN_COUNT)
+    return win_agg_run<i64>(fn, val, 0, cnt, d_part_start, d_lo, d_hi, n, d_out,
+                            nullptr);
+  if (dt == BG_DT_DECIMAL128)
+    return win_agg_run<i128>(fn, val, extremum, cnt, d_part_start, d_lo, d_hi,
+                             n, d_out, d_valid_out);
+  // a Float64 running sum restarts at every partition start, so one
+  // partition's magnitude never cancels into another's
+  if (dt == BG_DT_FLOAT64 && fn == BG_WIN_SUM)
+    return win_agg_run<double>(fn, val, 1, cnt, d_part_start, d_lo, d_hi, n,
+                               d_out, d_valid_out);
+  return win_agg_run<i64>(fn, val, extremum, cnt, d_part_start, d_lo, d_hi, n,
+                          d_out, d_valid_out);
+}

@@ -26,7 +26,8 @@
 //     crossing (multi_stream_reader.rs:17-34) and re-chunking to batch_size
 //     (:1194-1282) — the "shuffle" scan source, decompressing on device.
 //   * Operator semantics: FilterExec / ProjectionExec / HashJoinExec /
-//     AggregateExec(Partial|Final|Single) / SortExec(TopK) of DataFusion 55
+//     NestedLoopJoinExec / AggregateExec(Partial|Final|Single) /
+//     SortExec(TopK) / WindowAggExec + BoundedWindowAggExec of DataFusion 55
 //     (SURVEY.md §8a), each mapped onto the existing HIP kernels through
 //     the public C ABI only — this file contains no device code.
 //
@@ -2612,6 +2613,8 @@ static Table exec_sort(const Value& node, Metrics& m) {
   return gather_table(in, (const uint32_t*)perm->p, mrows);
 }
 
+static Table exec_window(const Value& node, Metrics& m);  // with its plan
+
 static Table exec_plan(const Value& node, Metrics& m) {
   const std::string op = node.get_str("op");
   if (op == "scan") {
@@ -2629,6 +2632,7 @@ static Table exec_plan(const Value& node, Metrics& m) {
     return exec_join(node, m);
   if (op == "hash_aggregate") return exec_aggregate(node, m);
   if (op == "sort") return exec_sort(node, m);
+  if (op == "window") return exec_window(node, m);
   if (op == "limit") {
     Table in = exec_plan(node.at("input"), m);
     int64_t lim = node.get_int("count");
@@ -3487,6 +3491,391 @@ static void validate_join_filter(const std::string& op, const VSchema& b,
   }
 }
 
+// ---------------------------------------------------------------------------
+// window: ranking and framed aggregates over sorted input (DataFusion's
+// WindowAggExec / BoundedWindowAggExec, Ballista's
+// PartitionedBoundedWindowAggExec).  plan_window is the one reading of the
+// node: bg_stage_validate and execution both go through it, so what
+// validation accepts is what runs.
+// ---------------------------------------------------------------------------
+
+struct WinBound {
+  int32_t kind = BG_WIN_UNBOUNDED;
+  bool is_int = true;  // how the plan spelled the offset
+  int64_t i = 0;
+  double d = 0.0;
+  bool offset() const { return kind >= BG_WIN_PRECEDING; }
+  // where the bound sits relative to the current row, for the ordering
+  // check only: preceding < 0 < following
+  double pos(bool is_start) const {
+    const double inf = 1e300;
+    switch (kind) {
+      case BG_WIN_UNBOUNDED: return is_start ? -inf : inf;
+      case BG_WIN_CURRENT_ROW: return 0.0;
+      case BG_WIN_PRECEDING: return -d;
+      default: return d;
+    }
+  }
+  std::string text(bool is_start) const {
+    auto num = [this]() {
+      if (is_int) return std::to_string(i);
+      char buf[32];
+      snprintf(buf, sizeof(buf), "%g", d);
+      return std::string(buf);
+    };
+    switch (kind) {
+      case BG_WIN_UNBOUNDED:
+        return is_start ? "unbounded preceding" : "unbounded following";
+      case BG_WIN_CURRENT_ROW: return "current row";
+      case BG_WIN_PRECEDING: return num() + " preceding";
+      default: return num() + " following";
+    }
+  }
+};
+
+struct WinFrame {
+  int32_t units = BG_WIN_ROWS;
+  WinBound start, end;
+  std::string text() const {
+    return std::string(units == BG_WIN_ROWS ? "rows" : "range") + " between " +
+           start.text(true) + " and " + end.text(false);
+  }
+  bool range_offset() const {
+    return units == BG_WIN_RANGE && (start.offset() || end.offset());
+  }
+};
+
+struct WinOrderKey {
+  std::string col;
+  bool desc, nulls_first;
+};
+
+struct WinExpr {
+  std::string fn, as;
+  bool ranking = false;
+  const Value* expr = nullptr;  // nullptr: ranking, or count(*)
+  WinFrame frame;
+  DtSpec in = DT_I64;  // the evaluated expression's dtype
+  DtSpec out = DT_I64;
+};
+
+struct WinPlan {
+  std::vector<std::string> part;
+  std::vector<WinOrderKey> order;
+  std::vector<WinExpr> exprs;
+};
+
+static WinBound parse_window_bound(const std::string& who, const Value& b) {
+  WinBound r;
+  if (b.kind == Value::STR) {
+    if (b.s == "unbounded") r.kind = BG_WIN_UNBOUNDED;
+    else if (b.s == "current_row") r.kind = BG_WIN_CURRENT_ROW;
+    else
+      throw StageError(BG_ERR_INVALID, who + ": unknown frame bound '" + b.s +
+                                           "'");
+    return r;
+  }
+  const bool prec = b.kind == Value::OBJ && b.has("preceding");
+  const bool foll = b.kind == Value::OBJ && b.has("following");
+  if (prec == foll)
+    throw StageError(BG_ERR_INVALID,
+                     who + ": a frame bound is \"unbounded\", \"current_row\", "
+                           "{preceding: N} or {following: N}");
+  r.kind = prec ? BG_WIN_PRECEDING : BG_WIN_FOLLOWING;
+  const Value& v = b.at(prec ? "preceding" : "following");
+  if (v.kind == Value::INT) {
+    r.i = v.i;
+    r.d = (double)v.i;
+  } else if (v.kind == Value::DBL) {
+    r.is_int = false;
+    r.d = v.d;
+  } else {
+    throw StageError(BG_ERR_INVALID, who + ": frame offset must be a number");
+  }
+  if (!(r.d >= 0.0))
+    throw StageError(BG_ERR_INVALID,
+                     who + ": negative frame offset (" + r.text(true) + ")");
+  return r;
+}
+
+// One frame, checked against the node's order keys; `who` names the node
+// and the expression in every refusal.
+static WinFrame parse_window_frame(const std::string& who, const Value& f,
+                                   const std::vector<DtSpec>& order_dts) {
+  WinFrame fr;
+  const std::string units = f.get_str("units");
+  if (units == "groups")
+    throw StageError(BG_ERR_UNSUPPORTED, who + ": frame units 'groups'");
+  if (units != "rows" && units != "range")
+    throw StageError(BG_ERR_INVALID,
+                     who + ": unknown frame units '" + units + "'");
+  fr.units = units == "rows" ? BG_WIN_ROWS : BG_WIN_RANGE;
+  fr.start = parse_window_bound(who, f.at("start"));
+  fr.end = parse_window_bound(who, f.at("end"));
+  if (fr.start.pos(true) > fr.end.pos(false))
+    throw StageError(BG_ERR_INVALID, who + ": frame start lies after its end (" +
+                                         fr.text() + ")");
+  if (fr.units == BG_WIN_ROWS) {
+    for (const WinBound* b : {&fr.start, &fr.end})
+      if (b->offset() && !b->is_int)
+        throw StageError(BG_ERR_INVALID,
+                         who + ": a rows offset must be an integer (" +
+                             fr.text() + ")");
+  }
+  if (fr.range_offset()) {
+    if (order_dts.size() != 1)
+      throw StageError(BG_ERR_INVALID,
+                       who + ": a range offset needs exactly one order_by "
+                             "key, the node has " +
+                           std::to_string(order_dts.size()) + " (" +
+                           fr.text() + ")");
+    const int32_t dt = order_dts[0].dt;
+    if (dt != BG_DT_INT64 && dt != BG_DT_INT32 && dt != BG_DT_DATE32 &&
+        dt != BG_DT_FLOAT64)
+      throw StageError(BG_ERR_UNSUPPORTED,
+                       who + ": a range offset over a " +
+                           std::string(dtype_name(dt)) + " order_by key (" +
+                           fr.text() + ")");
+    for (const WinBound* b : {&fr.start, &fr.end})
+      if (b->offset() && !b->is_int && dt != BG_DT_FLOAT64)
+        throw StageError(BG_ERR_INVALID,
+                         who + ": a fractional range offset over a " +
+                             std::string(dtype_name(dt)) + " order_by key (" +
+                             fr.text() + ")");
+  }
+  return fr;
+}
+
+// Whether fn runs over dt under this frame: the one dtype verdict.
+static void check_window_agg(const std::string& who, const std::string& fn,
+                             int32_t dt, const WinFrame& fr) {
+  if (fn == "count") return;  // reads validity only
+  if (fn == "min" || fn == "max") {
+    if (dt != BG_DT_INT64 && dt != BG_DT_INT32 && dt != BG_DT_DATE32 &&
+        dt != BG_DT_FLOAT64 && dt != BG_DT_DECIMAL128)
+      throw StageError(BG_ERR_UNSUPPORTED,
+                       who + ": " + fn + " over " + dtype_name(dt) + " (" +
+                           fr.text() + ")");
+    if (fr.start.kind != BG_WIN_UNBOUNDED)
+      throw StageError(BG_ERR_UNSUPPORTED,
+                       who + ": sliding " + fn + " (" + fr.text() +
+                           "); the frame must start at unbounded preceding");
+    return;
+  }
+  const bool ok = dt == BG_DT_DECIMAL128 || dt == BG_DT_FLOAT64 ||
+                  (dt == BG_DT_INT64 && fn == "sum");
+  if (!ok)
+    throw StageError(BG_ERR_UNSUPPORTED,
+                     who + ": " + fn + " over " + dtype_name(dt));
+}
+
+static const char* const WIN_RANK_FNS[] = {"row_number", "rank", "dense_rank"};
+
+static WinPlan plan_window(const Value& node, const VSchema& in) {
+  WinPlan p;
+  auto key_col = [&in](const char* list, const std::string& name) {
+    if (!schema_has(in, name))
+      throw StageError(BG_ERR_INVALID, std::string("window: ") + list +
+                                           " names unknown column '" + name +
+                                           "'");
+    return in.dts[(size_t)in.idx(name)];
+  };
+  auto& part = node.get_arr("partition_by");
+  auto& order = node.get_arr("order_by");
+  for (auto* l : {&part, &order})
+    if (l->size() > 4)
+      throw StageError(BG_ERR_INVALID,
+                       std::string("window: ") +
+                           (l == &part ? "partition_by" : "order_by") +
+                           " has " + std::to_string(l->size()) +
+                           " keys, at most 4");
+  for (auto& k : part) {
+    key_col("partition_by", k->s);
+    p.part.push_back(k->s);
+  }
+  std::vector<DtSpec> order_dts;
+  for (auto& k : order) {
+    const std::string col = k->get_str("col");
+    order_dts.push_back(key_col("order_by", col));
+    const bool d = k->get_bool_or("desc", false);
+    p.order.push_back({col, d, k->get_bool_or("nulls_first", d)});
+  }
+  auto& exprs = node.get_arr("exprs");
+  if (exprs.empty())
+    throw StageError(BG_ERR_INVALID, "window: 'exprs' is empty");
+  for (auto& ev : exprs) {
+    WinExpr e;
+    e.fn = ev->get_str("fn");
+    e.as = ev->get_str("as");
+    const std::string who = "window: " + e.fn + " as '" + e.as + "'";
+    if (schema_has(in, e.as))
+      throw StageError(BG_ERR_INVALID,
+                       who + ": the name collides with an input column");
+    for (auto& prev : p.exprs)
+      if (prev.as == e.as)
+        throw StageError(BG_ERR_INVALID, who + ": duplicate output name");
+    for (const char* r : WIN_RANK_FNS)
+      if (e.fn == r) e.ranking = true;
+    if (e.ranking) {
+      if (ev->has("expr"))
+        throw StageError(BG_ERR_INVALID, who + ": a ranking fn takes no expr");
+      p.exprs.push_back(e);
+      continue;
+    }
+    if (e.fn != "sum" && e.fn != "avg" && e.fn != "min" && e.fn != "max" &&
+        e.fn != "count")
+      throw StageError(BG_ERR_INVALID, who + ": unknown window fn");
+    if (!ev->has("frame"))
+      throw StageError(BG_ERR_INVALID, who + ": an aggregate needs a frame");
+    if (ev->has("expr")) e.expr = &ev->at("expr");
+    else if (e.fn != "count")
+      throw StageError(BG_ERR_INVALID, who + ": expr required");
+    e.frame = parse_window_frame(who, ev->at("frame"), order_dts);
+    if (e.expr) {
+      e.in = validate_expr(in, *e.expr);
+      if (is_literal_node(*e.expr))
+        throw StageError(BG_ERR_INVALID, who + ": bare literal expression");
+      check_window_agg(who, e.fn, e.in.dt, e.frame);
+    }
+    e.out = agg_output_fields(e.fn, "single", e.as, e.in)[0].dt;
+    p.exprs.push_back(e);
+  }
+  return p;
+}
+
+// the frame's [lo, hi) arrays; lo stays empty when the frame starts at the
+// partition start (bg_window_agg reads d_part_start then)
+struct WinFrameBufs {
+  std::string key;
+  DBufPtr lo, hi;
+};
+
+struct WinBounds {
+  DBufPtr ps, pe, qs, qe;
+  const uint32_t* u(const DBufPtr& b) const { return (const uint32_t*)b->p; }
+};
+
+static const WinFrameBufs& window_frame(const WinFrame& fr, const WinPlan& p,
+                                        const Table& in, const WinBounds& b,
+                                        std::vector<WinFrameBufs>& cache) {
+  const std::string key = fr.text();
+  for (auto& c : cache)
+    if (c.key == key) return c;
+  WinFrameBufs fb;
+  fb.key = key;
+  fb.lo = dalloc_elems(in.n, 4);
+  fb.hi = dalloc_elems(in.n, 4);
+  bg_column okey{};
+  bool f64 = false;
+  if (fr.range_offset()) {
+    okey = to_bg(in.col(p.order[0].col), in.n);
+    f64 = okey.dtype == BG_DT_FLOAT64;
+  }
+  auto off = [f64](const WinBound& w) {
+    if (!f64) return w.i;
+    int64_t bits;
+    memcpy(&bits, &w.d, 8);
+    return bits;
+  };
+  chk(bg_window_frame(fr.units, fr.start.kind, off(fr.start), fr.end.kind,
+                      off(fr.end), fr.range_offset() ? &okey : nullptr,
+                      !p.order.empty() && p.order[0].desc ? 1 : 0, b.u(b.ps),
+                      b.u(b.pe), b.u(b.qs), b.u(b.qe), in.n,
+                      (uint32_t*)fb.lo->p, (uint32_t*)fb.hi->p),
+      "bg_window_frame");
+  if (fr.start.kind == BG_WIN_UNBOUNDED) fb.lo = nullptr;
+  cache.push_back(std::move(fb));
+  return cache.back();
+}
+
+// one bg_window_agg call into a fresh column of dtype dt
+static Col window_agg_col(int32_t fn, const Col* val, const DtSpec& dt,
+                          const WinBounds& b, const WinFrameBufs& fb,
+                          int64_t n) {
+  Col c = make_col(dt);
+  c.data = dalloc_elems(n, dt_size(dt.dt));
+  if (fn != BG_WIN_COUNT) c.validity = alloc_bitmap(n);
+  bg_column v{};
+  if (val) v = to_bg(*val, n);
+  chk(bg_window_agg(fn, val ? &v : nullptr, b.u(b.ps),
+                    fb.lo ? (const uint32_t*)fb.lo->p : nullptr,
+                    (const uint32_t*)fb.hi->p, n, c.data->p,
+                    c.validity ? c.validity->u8() : nullptr),
+      "bg_window_agg");
+  return c;
+}
+
+static Table exec_window(const Value& node, Metrics& m) {
+  Table in = exec_plan(node.at("input"), m);
+  VSchema vs;
+  vs.names = in.names;
+  for (auto& c : in.cols) vs.dts.push_back(c.spec());
+  const WinPlan p = plan_window(node, vs);
+  const int64_t n = in.n;
+
+  std::vector<bg_column> pcols, ocols;
+  for (auto& k : p.part) pcols.push_back(to_bg(in.col(k), n));
+  for (auto& k : p.order) ocols.push_back(to_bg(in.col(k.col), n));
+  WinBounds b;
+  for (DBufPtr* d : {&b.ps, &b.pe, &b.qs, &b.qe}) *d = dalloc_elems(n, 4);
+  chk(bg_window_bounds(pcols.data(), (int32_t)pcols.size(), ocols.data(),
+                       (int32_t)ocols.size(), n, (uint32_t*)b.ps->p,
+                       (uint32_t*)b.pe->p, (uint32_t*)b.qs->p,
+                       (uint32_t*)b.qe->p),
+      "bg_window_bounds");
+
+  // the aggregates' inputs: arithmetic fuses into one pass, as in
+  // hash_aggregate
+  std::vector<const Value*> vexprs;
+  for (auto& e : p.exprs)
+    if (e.expr) vexprs.push_back(e.expr);
+  std::vector<Col> vcols;
+  if (!vexprs.empty()) eval_exprs_fused(in, vexprs, &vcols);
+
+  Table out = in;
+  std::vector<WinFrameBufs> frames;
+  size_t vi = 0;
+  for (auto& e : p.exprs) {
+    Col c;
+    if (e.ranking) {
+      c = make_col(DT_I64);
+      c.data = dalloc_elems(n, 8);
+      const int32_t fn = e.fn == "row_number" ? BG_WIN_ROW_NUMBER
+                         : e.fn == "rank"     ? BG_WIN_RANK
+                                              : BG_WIN_DENSE_RANK;
+      chk(bg_window_rank(fn, b.u(b.ps), b.u(b.qs), n, (int64_t*)c.data->p),
+          "bg_window_rank");
+    } else {
+      const Col* val = e.expr ? &vcols[vi++] : nullptr;
+      const WinFrameBufs& fb = window_frame(e.frame, p, in, b, frames);
+      if (e.fn == "avg") {
+        // SUM and COUNT per row, then the hash aggregate's own finalisation
+        // with one "group" per row
+        const DtSpec sum_dt =
+            agg_output_fields("sum", "single", e.as, e.in)[0].dt;
+        Col s = window_agg_col(BG_WIN_SUM, val, sum_dt, b, fb, n);
+        Col cnt = window_agg_col(BG_WIN_COUNT, val, DT_I64, b, fb, n);
+        c = make_col(e.out);
+        c.data = dalloc_elems(n, dt_size(e.out.dt));
+        c.validity = alloc_bitmap(n, 0xFF);
+        chk(bg_avg_finalize(s.data->p, dt_size(sum_dt.dt),
+                            e.out.dt == BG_DT_FLOAT64 ? 1 : 0, cnt.data->p, 8,
+                            4, n, c.data->p, c.validity->u8()),
+            "bg_avg_finalize");
+      } else {
+        const int32_t fn = e.fn == "sum"     ? BG_WIN_SUM
+                           : e.fn == "count" ? BG_WIN_COUNT
+                           : e.fn == "min"   ? BG_WIN_MIN
+                                             : BG_WIN_MAX;
+        c = window_agg_col(fn, val, e.out, b, fb, n);
+      }
+    }
+    out.names.push_back(e.as);
+    out.cols.push_back(std::move(c));
+  }
+  return out;
+}
+
 static VSchema validate_plan(const Value& node) {
   const std::string op = node.get_str("op");
   if (op == "scan") {
@@ -3583,6 +3972,15 @@ static VSchema validate_plan(const Value& node) {
   if (op == "sort") {
     VSchema s = validate_plan(node.at("input"));
     for (auto& k : node.get_arr("keys")) s.idx(k->get_str("col"));
+    return s;
+  }
+  if (op == "window") {
+    VSchema s = validate_plan(node.at("input"));
+    const WinPlan p = plan_window(node, s);
+    for (auto& e : p.exprs) {
+      s.names.push_back(e.as);
+      s.dts.push_back(e.out);
+    }
     return s;
   }
   if (op == "limit") return validate_plan(node.at("input"));

@@ -65,6 +65,20 @@ BG_AGG_OP_MAX_I32 = 8
 BG_AGG_OP_MIN_ROW = 9  # Decimal128/Utf8: acc word 0 = winning row + 1
 BG_AGG_OP_MAX_ROW = 10
 
+BG_WIN_ROW_NUMBER = 0
+BG_WIN_RANK = 1
+BG_WIN_DENSE_RANK = 2
+BG_WIN_ROWS = 0
+BG_WIN_RANGE = 1
+BG_WIN_UNBOUNDED = 0
+BG_WIN_CURRENT_ROW = 1
+BG_WIN_PRECEDING = 2
+BG_WIN_FOLLOWING = 3
+BG_WIN_SUM = 0
+BG_WIN_COUNT = 1
+BG_WIN_MIN = 2
+BG_WIN_MAX = 3
+
 BG_PROJ_MUL = 0
 BG_PROJ_ADD = 1
 BG_PROJ_SUB = 2
@@ -244,6 +258,8 @@ _SIGNATURES = {
     "bg_bitcopy": "i plpl", "bg_agg_materialize": "i plilpplp",
     "bg_agg_winner_rows": "i pllpp",
     "bg_copy_i64_strided": "i pllp", "bg_avg_finalize": "i pliplilpp",
+    "bg_window_bounds": "i pipilpppp", "bg_window_rank": "i ipplp",
+    "bg_window_frame": "i iililpipppplpp", "bg_window_agg": "i ipppplpp",
     "bg_execute_stage": "i sS", "bg_stage_free": "v s",
     "bg_stage_validate": "i sS", "bg_stage_register_table": "i spSil",
     "bg_stage_unregister_table": "i s", "bg_fill_rand": "i plLlli",
@@ -748,6 +764,45 @@ class GpuStageContext:
         _check(self.L.bg_sort_rows(karr, darr, len(key_cols), n, perm.ptr),
                "bg_sort_rows")
         return perm
+
+    # ---- window functions over sorted rows; buffers are the caller's ----
+    @staticmethod
+    def _ptr(buf):
+        return buf.ptr if buf is not None else None
+
+    def window_bounds(self, part_cols, order_cols, n, part_start=None,
+                      part_end=None, peer_start=None, peer_end=None):
+        """Partition / peer-group extents (u32[n] DeviceBuffers, any None)."""
+        parr = (BgColumn * max(len(part_cols), 1))(*part_cols)
+        oarr = (BgColumn * max(len(order_cols), 1))(*order_cols)
+        _check(self.L.bg_window_bounds(
+            parr, len(part_cols), oarr, len(order_cols), n,
+            self._ptr(part_start), self._ptr(part_end), self._ptr(peer_start),
+            self._ptr(peer_end)), "bg_window_bounds")
+
+    def window_rank(self, fn, part_start, peer_start, n, out):
+        _check(self.L.bg_window_rank(fn, self._ptr(part_start),
+                                     self._ptr(peer_start), n, out.ptr),
+               "bg_window_rank")
+
+    def window_frame(self, units, start, end, order_col, descending, bounds,
+                     n, lo, hi):
+        """start/end: (kind, offset); a float offset travels as its f64
+        bits.  bounds: (part_start, part_end, peer_start, peer_end)."""
+        def off(o):
+            return struct_unpack_bits(o) if isinstance(o, float) else int(o)
+        _check(self.L.bg_window_frame(
+            units, start[0], off(start[1]), end[0], off(end[1]),
+            ctypes.byref(order_col) if order_col is not None else None,
+            1 if descending else 0, *[self._ptr(b) for b in bounds], n,
+            lo.ptr, hi.ptr), "bg_window_frame")
+
+    def window_agg(self, fn, val, part_start, lo, hi, n, out, valid_out=None):
+        """val None = count(*); lo None = the frame starts at part_start."""
+        _check(self.L.bg_window_agg(
+            fn, ctypes.byref(val) if val is not None else None,
+            self._ptr(part_start), self._ptr(lo), hi.ptr, n, out.ptr,
+            self._ptr(valid_out)), "bg_window_agg")
 
     def merge_join(self, build_sorted: DeviceBuffer, nb: int,
                    probe_sorted: DeviceBuffer, np_: int):

@@ -916,6 +916,88 @@ int bg_avg_finalize(const void* d_sum_acc, int64_t acc_stride, int32_t is_f64,
                     int32_t scale_shift, int64_t ngroups, void* d_out,
                     uint8_t* d_valid_out);
 
+/* ---- window functions over sorted input ----
+ *
+ * DataFusion's BoundedWindowAggExec / WindowAggExec with
+ * InputOrderMode::Sorted (datafusion.proto WindowAggExecNode,
+ * PhysicalWindowExprNode, WindowFrame); Ballista's
+ * PartitionedBoundedWindowAggExec runs the former per partition.  The rows
+ * are ALREADY sorted by (partition keys, order keys) — bg_sort_rows2
+ * upstream — and, like the reference, nothing here verifies that: unsorted
+ * input gives meaningless values, never an index outside [0, n].
+ *
+ * The work splits three ways: bounds once per window node, a frame once per
+ * distinct frame, one rank or aggregate call per expression.  Row positions
+ * are uint32_t; n > UINT32_MAX - 1 is BG_ERR_INVALID; n == 0 succeeds and
+ * touches nothing.  Every temporary returns to the pool before the call
+ * returns, on error paths too. */
+
+/* Partition and peer-group extents by adjacent-row comparison of the key
+ * columns (0-4 each; Utf8 by bytes; NULL equals NULL; Float64 by bit
+ * pattern, so -0.0 and +0.0 differ and equal NaN patterns match).  Rows
+ * are in one partition iff all part_cols are equal, and peers iff they
+ * share a partition and all order_cols are equal.  Per row i the half-open
+ * extents [d_part_start[i], d_part_end[i]) and [d_peer_start[i],
+ * d_peer_end[i]); any output may be NULL. */
+int bg_window_bounds(const bg_column* part_cols, int32_t npart,
+                     const bg_column* order_cols, int32_t norder, int64_t n,
+                     uint32_t* d_part_start, uint32_t* d_part_end,
+                     uint32_t* d_peer_start, uint32_t* d_peer_end);
+
+#define BG_WIN_ROW_NUMBER 0
+#define BG_WIN_RANK 1
+#define BG_WIN_DENSE_RANK 2
+/* row_number / rank / dense_rank, 1-based, as INT64 (DataFusion types them
+ * UInt64; same bits, values < 2^32).  d_peer_start may be NULL for
+ * ROW_NUMBER; d_part_start NULL means one partition. */
+int bg_window_rank(int32_t fn, const uint32_t* d_part_start,
+                   const uint32_t* d_peer_start, int64_t n, int64_t* d_out);
+
+#define BG_WIN_ROWS 0
+#define BG_WIN_RANGE 1
+#define BG_WIN_UNBOUNDED 0   /* preceding as a start, following as an end */
+#define BG_WIN_CURRENT_ROW 1
+#define BG_WIN_PRECEDING 2
+#define BG_WIN_FOLLOWING 3
+/* Resolve one frame to a half-open row range [d_lo[i], d_hi[i]) inside the
+ * row's partition; always part_start <= lo <= hi <= part_end, and an empty
+ * frame is legal.  ROWS offsets count rows.  RANGE: CURRENT_ROW is the peer
+ * group's edge; an offset bound needs order_col, the single order key
+ * (INT64, INT32, DATE32 in days, or FLOAT64 with the offset passed as f64
+ * bits), and is found by a bounded binary search among the partition's
+ * non-NULL keys, key +/- offset saturating at the i64 limits; a row whose
+ * key is NULL keeps its NULL peer group as the offset side.  order_col is
+ * NULL unless a RANGE offset bound is present; offsets are >= 0 and read
+ * only for PRECEDING/FOLLOWING.  The peer arrays may be NULL for ROWS. */
+int bg_window_frame(int32_t units, int32_t start_kind, int64_t start_off,
+                    int32_t end_kind, int64_t end_off,
+                    const bg_column* order_col, int32_t descending,
+                    const uint32_t* d_part_start, const uint32_t* d_part_end,
+                    const uint32_t* d_peer_start, const uint32_t* d_peer_end,
+                    int64_t n, uint32_t* d_lo, uint32_t* d_hi);
+
+#define BG_WIN_SUM 0
+#define BG_WIN_COUNT 1
+#define BG_WIN_MIN 2
+#define BG_WIN_MAX 3
+/* One aggregate over every row's frame [lo, hi), NULL inputs skipped (AVG
+ * is SUM + COUNT + bg_avg_finalize with one "group" per row).  d_lo NULL
+ * means "the frame starts at d_part_start", and is REQUIRED for MIN/MAX:
+ * they are the segmented running extremum at hi - 1, and a sliding one is
+ * BG_ERR_UNSUPPORTED.  val NULL is count(*).
+ *   SUM   INT64 (wrapping) -> i64; DECIMAL128 (exact i128) -> 16 B;
+ *         FLOAT64 -> f64, its running prefix restarted per partition
+ *   COUNT -> i64, never NULL (d_valid_out unused, may be NULL)
+ *   MIN/MAX over INT64, INT32, DATE32, FLOAT64 (IEEE total order),
+ *         DECIMAL128 -> val's own width
+ * SUM/MIN/MAX clear a row's bit in d_valid_out when its frame holds no
+ * non-NULL input (the value written is 0); ceil(n/8) bytes are written
+ * whole and none beyond. */
+int bg_window_agg(int32_t fn, const bg_column* val,
+                  const uint32_t* d_part_start, const uint32_t* d_lo,
+                  const uint32_t* d_hi, int64_t n, void* d_out,
+                  uint8_t* d_valid_out);
+
 /* ---- stage interpreter (the product entry of SURVEY.md §8b seam 1) ----
  *
  * bg_execute_stage executes ONE whole query stage — the GPU analogue of
@@ -929,8 +1011,9 @@ int bg_avg_finalize(const void* d_sum_acc, int64_t acc_stride, int32_t is_f64,
  * plan (the Rust host decodes task.plan with datafusion-proto exactly as
  * execution_loop.rs:364-367 does, then serialises the operator tree to
  * this schema — see INTEGRATION.md "Stage plan JSON").  Operators:
- * scan / filter / project / hash_join / hash_aggregate / sort /
- * sort_shuffle_write / passthrough_write / collect.
+ * scan / filter / project / hash_join / nested_loop_join /
+ * hash_aggregate / sort / limit / window / sort_shuffle_write /
+ * passthrough_write / collect.
  *
  * On success *out_json receives a malloc'd result document:
  *   {"partitions": [{"partition_id", "path", "num_batches", "num_rows",
