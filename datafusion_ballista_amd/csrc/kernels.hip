@@ -7050,68 +7050,14 @@ __device__ __forceinline__ bool join_emits_unmatched_probe(int32_t jt) {
   return jt == BG_JOIN_ANTI || jt == BG_JOIN_OUTER_PROBE;
 }
 
-template <typename Filter>
-__global__ void k_join_count2(JoinProbeArgs t, int32_t join_type, Filter f,
-                              uint32_t* counts) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       i < t.n_probe; i += (int64_t)gridDim.x * blockDim.x) {
-    u64 cnt = 0;
-    join_walk(t, f, i, [&](int64_t) {
-      ++cnt;
-      return join_first_match_decides(join_type);
-    });
-    if (!join_emits_matches(join_type)) cnt = cnt ? 0 : 1;
-    else if (join_emits_unmatched_probe(join_type)) cnt = cnt ? cnt : 1;
-    counts[i] = (uint32_t)cnt;
-  }
-}
-
-// Writes the pairs k_join_count2 counted for the same join_type and filter.
-// MARK also marks every matched build row; it is launched for INNER and
-// OUTER_PROBE pairs only, so the first-match types compile out of it.
-template <typename Filter, bool MARK>
-__global__ void k_join_fill2(JoinProbeArgs t, int32_t join_type, Filter f,
-                             const i64* offsets, uint32_t* out_probe,
-                             uint32_t* out_build, uint32_t* visited) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       i < t.n_probe; i += (int64_t)gridDim.x * blockDim.x) {
-    i64 w = offsets[i];
-    bool matched = false;
-    join_walk(t, f, i, [&](int64_t b) {
-      matched = true;
-      if (MARK) mark_visited(visited, b);
-      if (!MARK && !join_emits_matches(join_type)) return true;
-      out_probe[w] = (uint32_t)i;
-      out_build[w] = (uint32_t)b;
-      ++w;
-      return !MARK && join_first_match_decides(join_type);
-    });
-    if (!matched && join_emits_unmatched_probe(join_type)) {
-      out_probe[w] = (uint32_t)i;
-      out_build[w] = BG_JOIN_NULL_IDX;
-    }
-  }
-}
-
-// Marks every matched build row and emits nothing: walks to the chain's end.
-template <typename Filter>
-__global__ void k_join_mark2(JoinProbeArgs t, Filter f, uint32_t* visited) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       i < t.n_probe; i += (int64_t)gridDim.x * blockDim.x)
-    join_walk(t, f, i, [&](int64_t b) {
-      mark_visited(visited, b);
-      return false;
-    });
-}
-
 // ---------------------------------------------------------------------------
 // Nested-loop join (NestedLoopJoinExec, datafusion.proto:1359-1365;
 // approved/q11.txt:69, q22.txt:14): a join without keys, so EVERY build row
 // is a candidate of every probe row and the residual filter alone decides.
-// It is the general probe above with a plain loop over the build rows in
-// place of the chain walk: the same filter policies, the same count ->
-// exclusive scan -> fill scheme, the same visited bitmap and the same
-// join-type helpers.
+// It is the general probe with a plain loop over the build rows in place of
+// the chain walk: the same probe kernels (below, over a walk policy), the
+// same filter policies, the same count -> exclusive scan -> fill scheme and
+// the same visited bitmap.
 //
 // Lanes own probe rows; the build index b runs 0 .. n_build-1 in a loop
 // whose control is wave-uniform, so a build row's mask bit, value and
@@ -7187,64 +7133,117 @@ struct NlJoinArgs {
   int64_t n_build, n_probe;
 };
 
-// Pair order of the nested-loop fill: ascending probe row, and within a
-// probe row ascending build row; an unmatched probe row (ANTI / OUTER_PROBE)
-// carries BG_JOIN_NULL_IDX.  The grid-stride loops below step by whole
-// blocks, so every wave enters the walk complete.
-template <typename Filter>
-__global__ void k_nl_join_count(NlJoinArgs t, int32_t join_type, Filter f,
-                                uint32_t* counts) {
-  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < t.n_probe;
-       base += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = base + threadIdx.x;
-    const bool active = i < t.n_probe;
+// Walk policies of the probe kernels: where the candidates of a probe row
+// come from, and with them how a kernel's lanes step through the probe rows,
+// because the two walks ask different things of that loop.
+//   rows(first, stride, fn)
+//              calls fn(i, active) for the probe rows of this lane; active
+//              is false where the lane is only kept in for its wave.  first
+//              is the block's first row and stride the grid's rows per step:
+//              the kernel reads them, because blockDim read in a member
+//              function is loaded per lane (+2 VGPRs in every instantiation,
+//              profiles/kernel_resource_usage_join_walk.txt).
+//   walk<MARK> calls match(build row) for every match of probe row i, in the
+//              walk's order, until match returns true ("stop"); MARK also
+//              sets the visited bit of every build row it reports.
+// The hash walk steps per lane: a lane past n_probe simply leaves, and
+// nothing a lane of JoinHashWalk reaches may hold a ballot.
+struct JoinHashWalk {
+  JoinProbeArgs t;
+  template <typename Fn>
+  __device__ __forceinline__ void rows(int64_t first, int64_t stride,
+                                       Fn&& fn) const {
+    for (int64_t i = first + threadIdx.x; i < t.n_probe; i += stride)
+      fn(i, true);
+  }
+  template <bool MARK, typename Filter, typename Match>
+  __device__ __forceinline__ void walk(const Filter& f, int64_t i, bool,
+                                       uint32_t* visited, Match&& match) const {
+    join_walk(t, f, i, [&](int64_t b) {
+      if (MARK) mark_visited(visited, b);
+      return match(b);
+    });
+  }
+};
+// The nested-loop walk steps by whole blocks, so every wave enters
+// nl_join_walk complete: a lane past n_probe stays in with active = false.
+// Marking is nl_join_walk<MARK>'s own (one ballot per build row).
+struct JoinNlWalk {
+  NlJoinArgs t;
+  template <typename Fn>
+  __device__ __forceinline__ void rows(int64_t first, int64_t stride,
+                                       Fn&& fn) const {
+    for (int64_t base = first; base < t.n_probe; base += stride) {
+      const int64_t i = base + threadIdx.x;
+      fn(i, i < t.n_probe);
+    }
+  }
+  template <bool MARK, typename Filter, typename Match>
+  __device__ __forceinline__ void walk(const Filter& f, int64_t i, bool active,
+                                       uint32_t* visited, Match&& match) const {
+    nl_join_walk<MARK>(t.n_build, f, i, active, visited, match);
+  }
+};
+
+// THE probe kernels of the general hash join and of the nested-loop join.
+// What a join type does with a match, with an unmatched probe row and when
+// its walk may stop is written here once per phase, for both walks and both
+// filter policies.  Pair order: ascending probe row; within a probe row the
+// walk's order (chain order, or ascending build row for the nested loop); an
+// unmatched probe row (ANTI / OUTER_PROBE) carries BG_JOIN_NULL_IDX.
+template <typename Walk, typename Filter>
+__global__ void k_join_count2(Walk w, int32_t join_type, Filter f,
+                              uint32_t* counts) {
+  const int64_t first = (int64_t)blockIdx.x * blockDim.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  w.rows(first, stride, [&](int64_t i, bool active) {
     u64 cnt = 0;
-    nl_join_walk<false>(t.n_build, f, i, active, nullptr, [&](int64_t) {
+    w.template walk<false>(f, i, active, nullptr, [&](int64_t) {
       ++cnt;
       return join_first_match_decides(join_type);
     });
     if (!join_emits_matches(join_type)) cnt = cnt ? 0 : 1;
     else if (join_emits_unmatched_probe(join_type)) cnt = cnt ? cnt : 1;
     if (active) counts[i] = (uint32_t)cnt;
-  }
+  });
 }
 
-// Writes the pairs k_nl_join_count counted for the same join_type and
-// filter.  MARK as in k_join_fill2: INNER and OUTER_PROBE pairs only.
-template <typename Filter, bool MARK>
-__global__ void k_nl_join_fill(NlJoinArgs t, int32_t join_type, Filter f,
-                               const i64* offsets, uint32_t* out_probe,
-                               uint32_t* out_build, uint32_t* visited) {
-  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < t.n_probe;
-       base += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = base + threadIdx.x;
-    const bool active = i < t.n_probe;
-    i64 w = active ? offsets[i] : 0;
+// Writes the pairs k_join_count2 counted for the same join_type and filter.
+// MARK also marks every matched build row; it is launched for INNER and
+// OUTER_PROBE pairs only, so the first-match types compile out of it.
+template <typename Walk, typename Filter, bool MARK>
+__global__ void k_join_fill2(Walk w, int32_t join_type, Filter f,
+                             const i64* offsets, uint32_t* out_probe,
+                             uint32_t* out_build, uint32_t* visited) {
+  const int64_t first = (int64_t)blockIdx.x * blockDim.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  w.rows(first, stride, [&](int64_t i, bool active) {
+    i64 slot = active ? offsets[i] : 0;
     bool matched = false;
-    nl_join_walk<MARK>(t.n_build, f, i, active, visited, [&](int64_t b) {
+    w.template walk<MARK>(f, i, active, visited, [&](int64_t b) {
       matched = true;
       if (!MARK && !join_emits_matches(join_type)) return true;
-      out_probe[w] = (uint32_t)i;
-      out_build[w] = (uint32_t)b;
-      ++w;
+      out_probe[slot] = (uint32_t)i;
+      out_build[slot] = (uint32_t)b;
+      ++slot;
       return !MARK && join_first_match_decides(join_type);
     });
     if (active && !matched && join_emits_unmatched_probe(join_type)) {
-      out_probe[w] = (uint32_t)i;
-      out_build[w] = BG_JOIN_NULL_IDX;
+      out_probe[slot] = (uint32_t)i;
+      out_build[slot] = BG_JOIN_NULL_IDX;
     }
-  }
+  });
 }
 
-// Marks every matched build row and emits nothing: walks every build row.
-template <typename Filter>
-__global__ void k_nl_join_mark(NlJoinArgs t, Filter f, uint32_t* visited) {
-  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < t.n_probe;
-       base += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = base + threadIdx.x;
-    nl_join_walk<true>(t.n_build, f, i, i < t.n_probe, visited,
-                       [&](int64_t) { return false; });
-  }
+// Marks every matched build row and emits nothing: walks every candidate.
+template <typename Walk, typename Filter>
+__global__ void k_join_mark2(Walk w, Filter f, uint32_t* visited) {
+  const int64_t first = (int64_t)blockIdx.x * blockDim.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  w.rows(first, stride, [&](int64_t i, bool active) {
+    w.template walk<true>(f, i, active, visited,
+                          [](int64_t) { return false; });
+  });
 }
 
 // ~visited (or all ones where nothing was ever marked) as a mask for the
@@ -7279,24 +7278,48 @@ static int keyargs_from_cols(const bg_column* cols, int32_t nkeys,
   return BG_OK;
 }
 
-struct BgJoinTable2 {
-  ulong2* nodes;
-  int* head;
-  int64_t n_build;
-  u64 mask;
-  KeyArgs bkeys;  // caller's device buffers must outlive the handle
-  int32_t nkeys;
+// What a handle keeps between its probe calls: the offsets between a count
+// and its fill, and the visited bitmap.  The nested-loop handle is this and
+// nothing more; the general hash handle adds its table and keys.
+struct JoinProbeState {
+  int64_t n_build = 0;
   i64* probe_offsets = nullptr;
   int64_t probe_n = 0;
   int32_t probe_jt = -1;
   // one visited bit per build row, ((n_build+63)/64)*8 + 8 bytes; allocated
-  // and zeroed by the first marking call, accumulated until free2
+  // and zeroed by the first marking call, accumulated until the handle's free
   uint32_t* visited = nullptr;
-  // the filter of the last bg_hashjoin_probe_count2_filtered, which stores
-  // probe_jt with JOIN_JT_FILTERED set: a fill must repeat both
+  // the filter of the last filtered count, which stores probe_jt with
+  // JOIN_JT_FILTERED set: a fill must repeat both
   JoinFilterArgs probe_filter = {};
 };
 #define JOIN_JT_FILTERED 0x100
+struct BgJoinTable2 : JoinProbeState {
+  ulong2* nodes;
+  int* head;
+  u64 mask;
+  KeyArgs bkeys;  // caller's device buffers must outlive the handle
+  int32_t nkeys;
+};
+using BgNlJoin = JoinProbeState;
+
+// The wording of the shared checks, which names each handle's own entries.
+struct JoinHandleText {
+  const char* count_first;           // a fill no unfiltered count sized
+  const char* count_first_filtered;  // a fill no filtered count sized
+  const char* no_pairs;              // SEMI_BUILD / ANTI_BUILD to count or fill
+};
+static const JoinHandleText kHashJoinText = {
+    "call bg_hashjoin_probe_count2 first (same join_type)",
+    "call bg_hashjoin_probe_count2_filtered first (same join_type, same "
+    "terms)",
+    "SEMI_BUILD/ANTI_BUILD emit no pairs: call bg_hashjoin_probe_mark2, then "
+    "bg_hashjoin_build_rows2"};
+static const JoinHandleText kNlJoinText = {
+    "call bg_nljoin_count first (same n_probe, same join_type, same terms)",
+    "call bg_nljoin_count first (same n_probe, same join_type, same terms)",
+    "SEMI_BUILD/ANTI_BUILD emit no pairs: call bg_nljoin_mark, then "
+    "bg_nljoin_build_rows"};
 
 static inline uint64_t join_visited_bytes(int64_t n_build) {
   return (uint64_t)((n_build + 63) / 64) * 8 + 8;
@@ -7304,14 +7327,19 @@ static inline uint64_t join_visited_bytes(int64_t n_build) {
 
 // lazily allocate + zero the visited bitmap (stream-ordered memset: every
 // marking kernel is launched on the same null stream after it)
-template <typename Table>
-static int join_ensure_visited(Table* t) {
+static int join_ensure_visited(JoinProbeState* t) {
   if (t->visited) return BG_OK;
   DevBuf<uint8_t> v;
   HIP_TRY(v.alloc((int64_t)join_visited_bytes(t->n_build)));
   HIP_TRY(hipMemsetAsync(v, 0, join_visited_bytes(t->n_build), 0));
   t->visited = reinterpret_cast<uint32_t*>(v.detach());
   return BG_OK;
+}
+
+// what either handle's free gives back to the pool for the probe state
+static void join_release_probe_state(JoinProbeState* t) {
+  if (t->probe_offsets) (void)pool_release(t->probe_offsets);
+  if (t->visited) (void)pool_release(t->visited);
 }
 
 // probe keys checked against the handle's build keys
@@ -7327,28 +7355,11 @@ static int join_probe_keys(const BgJoinTable2* t, const bg_column* keys,
   return BG_OK;
 }
 
-// What every general probe entry checks first, before anything is allocated
-// or launched: the handle, and the probe keys against the build's.  -> the
-// kernels' view of the table and of this call's probe rows.
-static int join_probe_args(void* handle, const bg_column* keys, int32_t nkeys,
-                           int64_t n, JoinProbeArgs* a) {
-  const BgJoinTable2* t = (const BgJoinTable2*)handle;
-  if (!t) return set_err(BG_ERR_INVALID, "null join handle");
-  a->bkeys = t->bkeys;
-  a->n_probe = n;
-  a->head = t->head;
-  a->nodes = t->nodes;
-  a->mask = t->mask;
-  return join_probe_keys(t, keys, nkeys, &a->pkeys);
-}
-
 // The count and fill entries take the pair-emitting types only: SEMI_BUILD /
 // ANTI_BUILD emit build rows, never pairs.
-static int join_check_pair_type(int32_t jt) {
+static int join_check_pair_type(int32_t jt, const JoinHandleText& text) {
   if (jt == BG_JOIN_SEMI_BUILD || jt == BG_JOIN_ANTI_BUILD)
-    return set_err(BG_ERR_INVALID,
-                   "SEMI_BUILD/ANTI_BUILD emit no pairs: call "
-                   "bg_hashjoin_probe_mark2, then bg_hashjoin_build_rows2");
+    return set_err(BG_ERR_INVALID, text.no_pairs);
   if (jt < BG_JOIN_INNER || jt > BG_JOIN_OUTER_FULL)
     return set_err(BG_ERR_INVALID, "unknown join_type");
   return BG_OK;
@@ -7396,17 +7407,15 @@ extern "C" int bg_hashjoin_free2(void* handle) {
   if (!t) return BG_OK;
   (void)pool_release(t->nodes);
   (void)pool_release(t->head);
-  if (t->probe_offsets) (void)pool_release(t->probe_offsets);
-  if (t->visited) (void)pool_release(t->visited);
+  join_release_probe_state(t);
   delete t;
   return BG_OK;
 }
 
 // The build rows of either visited-bitmap handle whose bit == matched, in
 // ascending build order; bits at or beyond n_build are never reported.
-template <typename Table>
-static int join_build_rows(Table* t, int32_t matched, int64_t* out_count,
-                           uint32_t* d_out_build) {
+static int join_build_rows(JoinProbeState* t, int32_t matched,
+                           int64_t* out_count, uint32_t* d_out_build) {
   if (!t || !out_count)
     return set_err(BG_ERR_INVALID, "null join handle / out_count");
   if (matched != 0 && matched != 1)
@@ -7511,15 +7520,17 @@ static void join_with_filter(const JoinFilterArgs* f, Run&& run) {
   else run(JoinNoFilter{});
 }
 
-// Count, fill and mark of a checked call; f is null without a filter.
-static int join_count(BgJoinTable2* t, const JoinProbeArgs& a,
-                      int32_t join_type, const JoinFilterArgs* f,
-                      int64_t* out_matches) {
+// Count, fill and mark of a checked call on either handle: w is the handle's
+// walk over this call's probe rows, f is null without a filter.
+template <typename Walk>
+static int join_count(JoinProbeState* t, const Walk& w, int32_t join_type,
+                      const JoinFilterArgs* f, int64_t* out_matches) {
   if (!out_matches) return set_err(BG_ERR_INVALID, "null out_matches");
-  int rc = join_count_phase(t, a.n_probe, out_matches, [&](uint32_t* counts) {
+  const int64_t n = w.t.n_probe;
+  int rc = join_count_phase(t, n, out_matches, [&](uint32_t* counts) {
     join_with_filter(f, [&](auto filter) {
-      hipLaunchKernelGGL(k_join_count2<decltype(filter)>,
-                         dim3(grid_for(a.n_probe)), dim3(BG_BLOCK), 0, 0, a,
+      hipLaunchKernelGGL((k_join_count2<Walk, decltype(filter)>),
+                         dim3(grid_for(n)), dim3(BG_BLOCK), 0, 0, w,
                          join_pair_type(join_type), filter, counts);
     });
   });
@@ -7530,17 +7541,17 @@ static int join_count(BgJoinTable2* t, const JoinProbeArgs& a,
   return BG_OK;
 }
 
-static int join_fill(BgJoinTable2* t, const JoinProbeArgs& a,
-                     int32_t join_type, const JoinFilterArgs* f,
+template <typename Walk>
+static int join_fill(JoinProbeState* t, const Walk& w, int32_t join_type,
+                     const JoinFilterArgs* f, const JoinHandleText& text,
                      uint32_t* d_out_probe, uint32_t* d_out_build) {
+  const int64_t n = w.t.n_probe;
   // the offsets are only good for the type and filter they were counted under
-  if (!t->probe_offsets || t->probe_n != a.n_probe ||
+  if (!t->probe_offsets || t->probe_n != n ||
       t->probe_jt != (f ? join_type | JOIN_JT_FILTERED : join_type) ||
       (f && memcmp(f, &t->probe_filter, sizeof(*f)) != 0))
     return set_err(BG_ERR_INVALID,
-                   f ? "call bg_hashjoin_probe_count2_filtered first (same "
-                       "join_type, same terms)"
-                     : "call bg_hashjoin_probe_count2 first (same join_type)");
+                   f ? text.count_first_filtered : text.count_first);
   const bool mark = join_type_marks(join_type);
   if (mark) {
     int rc = join_ensure_visited(t);
@@ -7548,27 +7559,53 @@ static int join_fill(BgJoinTable2* t, const JoinProbeArgs& a,
   }
   join_with_filter(f, [&](auto filter) {
     using F = decltype(filter);
-    hipLaunchKernelGGL((mark ? k_join_fill2<F, true> : k_join_fill2<F, false>),
-                       dim3(grid_for(a.n_probe)), dim3(BG_BLOCK), 0, 0, a,
-                       join_pair_type(join_type), filter, t->probe_offsets,
-                       d_out_probe, d_out_build, t->visited);
+    hipLaunchKernelGGL(
+        (mark ? k_join_fill2<Walk, F, true> : k_join_fill2<Walk, F, false>),
+        dim3(grid_for(n)), dim3(BG_BLOCK), 0, 0, w, join_pair_type(join_type),
+        filter, t->probe_offsets, d_out_probe, d_out_build, t->visited);
   });
   HIP_TRY(hipGetLastError());
   return BG_OK;
 }
 
-static int join_mark(BgJoinTable2* t, const JoinProbeArgs& a,
+template <typename Walk>
+static int join_mark(JoinProbeState* t, const Walk& w,
                      const JoinFilterArgs* f) {
   int rc = join_ensure_visited(t);
   if (rc != BG_OK) return rc;
-  if (a.n_probe <= 0) return BG_OK;
+  const int64_t n = w.t.n_probe;
+  if (n <= 0) return BG_OK;
   join_with_filter(f, [&](auto filter) {
-    hipLaunchKernelGGL(k_join_mark2<decltype(filter)>,
-                       dim3(grid_for(a.n_probe)), dim3(BG_BLOCK), 0, 0, a,
-                       filter, t->visited);
+    hipLaunchKernelGGL((k_join_mark2<Walk, decltype(filter)>),
+                       dim3(grid_for(n)), dim3(BG_BLOCK), 0, 0, w, filter,
+                       t->visited);
   });
   HIP_TRY(hipGetLastError());
   return BG_OK;
+}
+
+// What every general hash probe entry checks first, before anything is
+// allocated or launched: the handle, the probe keys against the build's,
+// the pair type of a count or fill (pair_type null: a mark entry, which has
+// none) and, for a _filtered entry (f not null), its terms.  -> the walk over
+// this call's probe rows and, filtered, the filter.
+static int hashjoin_check(void* handle, const bg_column* keys, int32_t nkeys,
+                          int64_t n, const int32_t* pair_type,
+                          const bg_join_filter_term* terms, int32_t nterms,
+                          JoinHashWalk* w, JoinFilterArgs* f) {
+  const BgJoinTable2* t = (const BgJoinTable2*)handle;
+  if (!t) return set_err(BG_ERR_INVALID, "null join handle");
+  w->t.bkeys = t->bkeys;
+  w->t.n_probe = n;
+  w->t.head = t->head;
+  w->t.nodes = t->nodes;
+  w->t.mask = t->mask;
+  int rc = join_probe_keys(t, keys, nkeys, &w->t.pkeys);
+  if (rc == BG_OK && pair_type)
+    rc = join_check_pair_type(*pair_type, kHashJoinText);
+  if (rc == BG_OK && f)
+    rc = join_filter_args(terms, nterms, t->n_build, n, f);
+  return rc;
 }
 
 extern "C" int bg_hashjoin_probe_count2(void* handle, const bg_column* keys,
@@ -7576,11 +7613,11 @@ extern "C" int bg_hashjoin_probe_count2(void* handle, const bg_column* keys,
                                         int32_t join_type,
                                         int64_t* out_matches) {
   REQUIRE_INIT();
-  JoinProbeArgs a;
-  int rc = join_probe_args(handle, keys, nkeys, n, &a);
-  if (rc == BG_OK) rc = join_check_pair_type(join_type);
+  JoinHashWalk w;
+  int rc = hashjoin_check(handle, keys, nkeys, n, &join_type, nullptr, 0, &w,
+                          nullptr);
   if (rc != BG_OK) return rc;
-  return join_count((BgJoinTable2*)handle, a, join_type, nullptr, out_matches);
+  return join_count((BgJoinTable2*)handle, w, join_type, nullptr, out_matches);
 }
 
 extern "C" int bg_hashjoin_probe_fill2(void* handle, const bg_column* keys,
@@ -7589,21 +7626,22 @@ extern "C" int bg_hashjoin_probe_fill2(void* handle, const bg_column* keys,
                                        uint32_t* d_out_probe,
                                        uint32_t* d_out_build) {
   REQUIRE_INIT();
-  JoinProbeArgs a;
-  int rc = join_probe_args(handle, keys, nkeys, n, &a);
-  if (rc == BG_OK) rc = join_check_pair_type(join_type);
+  JoinHashWalk w;
+  int rc = hashjoin_check(handle, keys, nkeys, n, &join_type, nullptr, 0, &w,
+                          nullptr);
   if (rc != BG_OK) return rc;
-  return join_fill((BgJoinTable2*)handle, a, join_type, nullptr, d_out_probe,
-                   d_out_build);
+  return join_fill((BgJoinTable2*)handle, w, join_type, nullptr,
+                   kHashJoinText, d_out_probe, d_out_build);
 }
 
 extern "C" int bg_hashjoin_probe_mark2(void* handle, const bg_column* keys,
                                        int32_t nkeys, int64_t n) {
   REQUIRE_INIT();
-  JoinProbeArgs a;
-  int rc = join_probe_args(handle, keys, nkeys, n, &a);
+  JoinHashWalk w;
+  int rc = hashjoin_check(handle, keys, nkeys, n, nullptr, nullptr, 0, &w,
+                          nullptr);
   if (rc != BG_OK) return rc;
-  return join_mark((BgJoinTable2*)handle, a, nullptr);
+  return join_mark((BgJoinTable2*)handle, w, nullptr);
 }
 
 extern "C" int bg_hashjoin_probe_count2_filtered(
@@ -7611,14 +7649,12 @@ extern "C" int bg_hashjoin_probe_count2_filtered(
     int32_t join_type, const bg_join_filter_term* terms, int32_t nterms,
     int64_t* out_matches) {
   REQUIRE_INIT();
-  BgJoinTable2* t = (BgJoinTable2*)handle;
-  JoinProbeArgs a;
+  JoinHashWalk w;
   JoinFilterArgs f;
-  int rc = join_probe_args(handle, keys, nkeys, n, &a);
-  if (rc == BG_OK) rc = join_check_pair_type(join_type);
-  if (rc == BG_OK) rc = join_filter_args(terms, nterms, t->n_build, n, &f);
+  int rc = hashjoin_check(handle, keys, nkeys, n, &join_type, terms, nterms,
+                          &w, &f);
   if (rc != BG_OK) return rc;
-  return join_count(t, a, join_type, &f, out_matches);
+  return join_count((BgJoinTable2*)handle, w, join_type, &f, out_matches);
 }
 
 extern "C" int bg_hashjoin_probe_fill2_filtered(
@@ -7626,66 +7662,50 @@ extern "C" int bg_hashjoin_probe_fill2_filtered(
     int32_t join_type, const bg_join_filter_term* terms, int32_t nterms,
     uint32_t* d_out_probe, uint32_t* d_out_build) {
   REQUIRE_INIT();
-  BgJoinTable2* t = (BgJoinTable2*)handle;
-  JoinProbeArgs a;
+  JoinHashWalk w;
   JoinFilterArgs f;
-  int rc = join_probe_args(handle, keys, nkeys, n, &a);
-  if (rc == BG_OK) rc = join_check_pair_type(join_type);
-  if (rc == BG_OK) rc = join_filter_args(terms, nterms, t->n_build, n, &f);
+  int rc = hashjoin_check(handle, keys, nkeys, n, &join_type, terms, nterms,
+                          &w, &f);
   if (rc != BG_OK) return rc;
-  return join_fill(t, a, join_type, &f, d_out_probe, d_out_build);
+  return join_fill((BgJoinTable2*)handle, w, join_type, &f, kHashJoinText,
+                   d_out_probe, d_out_build);
 }
 
 extern "C" int bg_hashjoin_probe_mark2_filtered(
     void* handle, const bg_column* keys, int32_t nkeys, int64_t n,
     const bg_join_filter_term* terms, int32_t nterms) {
   REQUIRE_INIT();
-  BgJoinTable2* t = (BgJoinTable2*)handle;
-  JoinProbeArgs a;
+  JoinHashWalk w;
   JoinFilterArgs f;
-  int rc = join_probe_args(handle, keys, nkeys, n, &a);
-  if (rc == BG_OK) rc = join_filter_args(terms, nterms, t->n_build, n, &f);
+  int rc = hashjoin_check(handle, keys, nkeys, n, nullptr, terms, nterms, &w,
+                          &f);
   if (rc != BG_OK) return rc;
-  return join_mark(t, a, &f);
+  return join_mark((BgJoinTable2*)handle, w, &f);
 }
 
 // ---- nested-loop join: host side ----
-// The handle owns what the general hash-join handle owns minus the table:
-// the offsets between count and fill, and the visited bitmap.
-struct BgNlJoin {
-  int64_t n_build = 0;
-  i64* probe_offsets = nullptr;
-  int64_t probe_n = 0;
-  int32_t probe_jt = -1;  // JOIN_JT_FILTERED set: counted with probe_filter
-  uint32_t* visited = nullptr;
-  JoinFilterArgs probe_filter = {};
-};
 
 // What every bg_nljoin_* probe entry checks first, before anything is
-// allocated or launched; terms == none (nterms 0) is a cross join.
-// *has_filter tells whether *f was filled.
+// allocated or launched; terms == none (nterms 0) is a cross join.  pair_type
+// as in hashjoin_check.  -> the walk over this call's probe rows and the
+// filter, null for a cross join (*f is its storage).
 static int nljoin_check(void* handle, int64_t n_probe,
                         const bg_join_filter_term* terms, int32_t nterms,
-                        JoinFilterArgs* f, bool* has_filter) {
+                        const int32_t* pair_type, JoinNlWalk* w,
+                        JoinFilterArgs* f, const JoinFilterArgs** filter) {
   const BgNlJoin* t = (const BgNlJoin*)handle;
   if (!t) return set_err(BG_ERR_INVALID, "null nested-loop join handle");
   if (n_probe < 0)
     return set_err(BG_ERR_INVALID, "nested-loop join: negative n_probe");
   if (nterms < 0)
     return set_err(BG_ERR_INVALID, "nested-loop join: negative nterms");
-  *has_filter = nterms > 0;
-  if (nterms == 0) return BG_OK;
-  return join_filter_args(terms, nterms, t->n_build, n_probe, f);
-}
-
-static int nljoin_check_pair_type(int32_t jt) {
-  if (jt == BG_JOIN_SEMI_BUILD || jt == BG_JOIN_ANTI_BUILD)
-    return set_err(BG_ERR_INVALID,
-                   "SEMI_BUILD/ANTI_BUILD emit no pairs: call "
-                   "bg_nljoin_mark, then bg_nljoin_build_rows");
-  if (jt < BG_JOIN_INNER || jt > BG_JOIN_OUTER_FULL)
-    return set_err(BG_ERR_INVALID, "unknown join_type");
-  return BG_OK;
+  w->t = NlJoinArgs{t->n_build, n_probe};
+  *filter = nterms > 0 ? f : nullptr;
+  int rc = BG_OK;
+  if (nterms > 0) rc = join_filter_args(terms, nterms, t->n_build, n_probe, f);
+  if (rc == BG_OK && pair_type)
+    rc = join_check_pair_type(*pair_type, kNlJoinText);
+  return rc;
 }
 
 extern "C" int bg_nljoin_open(int64_t n_build, void** out_handle) {
@@ -7707,8 +7727,7 @@ extern "C" int bg_nljoin_free(void* handle) {
   REQUIRE_INIT();
   BgNlJoin* t = (BgNlJoin*)handle;
   if (!t) return BG_OK;
-  if (t->probe_offsets) (void)pool_release(t->probe_offsets);
-  if (t->visited) (void)pool_release(t->visited);
+  join_release_probe_state(t);
   delete t;
   return BG_OK;
 }
@@ -7718,26 +7737,13 @@ extern "C" int bg_nljoin_count(void* handle, int64_t n_probe,
                                const bg_join_filter_term* terms,
                                int32_t nterms, int64_t* out_matches) {
   REQUIRE_INIT();
-  BgNlJoin* t = (BgNlJoin*)handle;
+  JoinNlWalk w;
   JoinFilterArgs f;
-  bool filtered = false;
-  int rc = nljoin_check(handle, n_probe, terms, nterms, &f, &filtered);
-  if (rc == BG_OK) rc = nljoin_check_pair_type(join_type);
+  const JoinFilterArgs* filter;
+  int rc = nljoin_check(handle, n_probe, terms, nterms, &join_type, &w, &f,
+                        &filter);
   if (rc != BG_OK) return rc;
-  if (!out_matches) return set_err(BG_ERR_INVALID, "null out_matches");
-  const NlJoinArgs a{t->n_build, n_probe};
-  rc = join_count_phase(t, n_probe, out_matches, [&](uint32_t* counts) {
-    join_with_filter(filtered ? &f : nullptr, [&](auto filter) {
-      hipLaunchKernelGGL(k_nl_join_count<decltype(filter)>,
-                         dim3(grid_for(n_probe)), dim3(BG_BLOCK), 0, 0, a,
-                         join_pair_type(join_type), filter, counts);
-    });
-  });
-  if (rc != BG_OK) return rc;
-  // a fill must repeat the type and, with JOIN_JT_FILTERED, the filter
-  t->probe_jt = filtered ? join_type | JOIN_JT_FILTERED : join_type;
-  if (filtered) t->probe_filter = f;
-  return BG_OK;
+  return join_count((BgNlJoin*)handle, w, join_type, filter, out_matches);
 }
 
 extern "C" int bg_nljoin_fill(void* handle, int64_t n_probe,
@@ -7746,56 +7752,27 @@ extern "C" int bg_nljoin_fill(void* handle, int64_t n_probe,
                               int32_t nterms, uint32_t* d_out_probe,
                               uint32_t* d_out_build) {
   REQUIRE_INIT();
-  BgNlJoin* t = (BgNlJoin*)handle;
+  JoinNlWalk w;
   JoinFilterArgs f;
-  bool filtered = false;
-  int rc = nljoin_check(handle, n_probe, terms, nterms, &f, &filtered);
-  if (rc == BG_OK) rc = nljoin_check_pair_type(join_type);
+  const JoinFilterArgs* filter;
+  int rc = nljoin_check(handle, n_probe, terms, nterms, &join_type, &w, &f,
+                        &filter);
   if (rc != BG_OK) return rc;
-  // the offsets are only good for the type and filter they were counted under
-  if (!t->probe_offsets || t->probe_n != n_probe ||
-      t->probe_jt != (filtered ? join_type | JOIN_JT_FILTERED : join_type) ||
-      (filtered && memcmp(&f, &t->probe_filter, sizeof(f)) != 0))
-    return set_err(BG_ERR_INVALID,
-                   "call bg_nljoin_count first (same n_probe, same "
-                   "join_type, same terms)");
-  const bool mark = join_type_marks(join_type);
-  if (mark) {
-    rc = join_ensure_visited(t);
-    if (rc != BG_OK) return rc;
-  }
-  const NlJoinArgs a{t->n_build, n_probe};
-  join_with_filter(filtered ? &f : nullptr, [&](auto filter) {
-    using F = decltype(filter);
-    hipLaunchKernelGGL(
-        (mark ? k_nl_join_fill<F, true> : k_nl_join_fill<F, false>),
-        dim3(grid_for(n_probe)), dim3(BG_BLOCK), 0, 0, a,
-        join_pair_type(join_type), filter, t->probe_offsets, d_out_probe,
-        d_out_build, t->visited);
-  });
-  HIP_TRY(hipGetLastError());
-  return BG_OK;
+  return join_fill((BgNlJoin*)handle, w, join_type, filter, kNlJoinText,
+                   d_out_probe, d_out_build);
 }
 
 extern "C" int bg_nljoin_mark(void* handle, int64_t n_probe,
                               const bg_join_filter_term* terms,
                               int32_t nterms) {
   REQUIRE_INIT();
-  BgNlJoin* t = (BgNlJoin*)handle;
+  JoinNlWalk w;
   JoinFilterArgs f;
-  bool filtered = false;
-  int rc = nljoin_check(handle, n_probe, terms, nterms, &f, &filtered);
-  if (rc == BG_OK) rc = join_ensure_visited(t);
+  const JoinFilterArgs* filter;
+  int rc = nljoin_check(handle, n_probe, terms, nterms, nullptr, &w, &f,
+                        &filter);
   if (rc != BG_OK) return rc;
-  if (n_probe == 0) return BG_OK;
-  const NlJoinArgs a{t->n_build, n_probe};
-  join_with_filter(filtered ? &f : nullptr, [&](auto filter) {
-    hipLaunchKernelGGL(k_nl_join_mark<decltype(filter)>,
-                       dim3(grid_for(n_probe)), dim3(BG_BLOCK), 0, 0, a,
-                       filter, t->visited);
-  });
-  HIP_TRY(hipGetLastError());
-  return BG_OK;
+  return join_mark((BgNlJoin*)handle, w, filter);
 }
 
 extern "C" int bg_nljoin_build_rows(void* handle, int32_t matched,

@@ -8,7 +8,6 @@ when the filter is TRUE (NULL counts as FALSE), and each join type reads
 import ctypes
 import decimal
 import gc
-import operator
 from collections import Counter, defaultdict
 
 import numpy as np
@@ -16,19 +15,12 @@ import pyarrow as pa
 import pytest
 
 from datafusion_ballista_amd import gpu, stage
+from join_filter_helpers import (
+    ANTI, ANTI_BUILD, BG_ERR_INVALID, BG_OK, CMP_CODE, I64, INNER, NULL_IDX,
+    OPS, OUTER_BUILD, OUTER_FULL, OUTER_PROBE, SEMI, SEMI_BUILD, SENTINEL,
+    bits, scan_of, term, terms_array)
 
 pytestmark = pytest.mark.gpu
-
-BG_OK, BG_ERR_INVALID = 0, -3
-INNER, SEMI, ANTI, OUTER_PROBE = 0, 1, 2, 3
-SEMI_BUILD, ANTI_BUILD, OUTER_BUILD, OUTER_FULL = 4, 5, 6, 7
-NULL_IDX = 0xFFFFFFFF
-SENTINEL = 0xDEADBEEF
-I64 = ctypes.c_int64
-OPS = {"lt": operator.lt, "le": operator.le, "gt": operator.gt,
-       "ge": operator.ge, "eq": operator.eq, "ne": operator.ne}
-CMP_CODE = {"lt": gpu.BG_CMP_LT, "le": gpu.BG_CMP_LE, "gt": gpu.BG_CMP_GT,
-            "ge": gpu.BG_CMP_GE, "eq": gpu.BG_CMP_EQ, "ne": gpu.BG_CMP_NE}
 
 
 @pytest.fixture(scope="module")
@@ -57,14 +49,6 @@ def reg(ctx):
 # ---------------------------------------------------------------------------
 def cols(*cs):
     return (gpu.BgColumn * len(cs))(*cs)
-
-
-def bits(flags):
-    """bool[n] -> Arrow LSB bitmap, padded like every mask here."""
-    n = len(flags)
-    out = np.zeros((n + 63) // 64 * 8 + 8, dtype=np.uint8)
-    out[:(n + 7) // 8] = np.packbits(flags, bitorder="little")
-    return out
 
 
 class Case:
@@ -189,16 +173,6 @@ DTYPES = {"int64": (gpu.BG_DT_INT64, enc_int64),
           "date32": (gpu.BG_DT_DATE32, enc_date32),
           "dict8": (gpu.BG_DT_DICT8, enc_dict8),
           "decimal128": (gpu.BG_DT_DECIMAL128, enc_dec128)}
-
-
-def term(kind, group, dtype=0, cmp=0, b=None, bv=None, p=None, pv=None):
-    ptr = lambda buf: buf.ptr.value if buf is not None else None  # noqa: E731
-    return gpu.BgJoinFilterTerm(kind, group, dtype, cmp, ptr(b), ptr(bv),
-                                ptr(p), ptr(pv))
-
-
-def terms_array(terms):
-    return (gpu.BgJoinFilterTerm * max(len(terms), 1))(*terms)
 
 
 class Dev:
@@ -538,11 +512,6 @@ def test_refusals_and_pool_balance(ctx):
 def _doc(plan):
     return {"job_id": "job-jf", "stage_id": 1, "task_id": 0,
             "work_dir": "/tmp/stage-tests", "plan": plan}
-
-
-def scan_of(table, name):
-    return {"op": "scan", "schema": stage.schema_json(table.schema),
-            "source": {"kind": "device", "table": name}}
 
 
 def run(plan):

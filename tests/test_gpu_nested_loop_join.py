@@ -6,32 +6,26 @@ row, probe row) pair is a candidate, it passes when the filter is TRUE (NULL
 counts as FALSE, no filter passes everything), and each join type reads
 "match" as "passing candidate".  Pairs come in ascending probe row and,
 within one, ascending build row."""
+import contextlib
 import ctypes
 import decimal
 import gc
-import operator
-from collections import Counter
+from collections import Counter, defaultdict
 
 import numpy as np
 import pyarrow as pa
 import pytest
 
 from datafusion_ballista_amd import gpu, stage
+from join_filter_helpers import (
+    ANTI, ANTI_BUILD, BG_ERR_INVALID, BG_OK, CMP_CODE, I64, INNER, NULL_IDX,
+    OPS, OUTER_BUILD, OUTER_FULL, OUTER_PROBE, SEMI, SEMI_BUILD, SENTINEL,
+    bits, scan_of, term, terms_array)
 
 pytestmark = pytest.mark.gpu
 
-BG_OK, BG_ERR_INVALID = 0, -3
-INNER, SEMI, ANTI, OUTER_PROBE = 0, 1, 2, 3
-SEMI_BUILD, ANTI_BUILD, OUTER_BUILD, OUTER_FULL = 4, 5, 6, 7
-NULL_IDX = 0xFFFFFFFF
-SENTINEL = 0xDEADBEEF
-I64 = ctypes.c_int64
 D = decimal.Decimal
 CTX = decimal.Context(prec=60)
-OPS = {"lt": operator.lt, "le": operator.le, "gt": operator.gt,
-       "ge": operator.ge, "eq": operator.eq, "ne": operator.ne}
-CMP_CODE = {"lt": gpu.BG_CMP_LT, "le": gpu.BG_CMP_LE, "gt": gpu.BG_CMP_GT,
-            "ge": gpu.BG_CMP_GE, "eq": gpu.BG_CMP_EQ, "ne": gpu.BG_CMP_NE}
 
 
 @pytest.fixture(scope="module")
@@ -58,14 +52,6 @@ def reg(ctx):
 # ---------------------------------------------------------------------------
 # ABI level: data, reference, device side
 # ---------------------------------------------------------------------------
-def bits(flags):
-    """bool[n] -> Arrow LSB bitmap, padded like every mask here."""
-    n = len(flags)
-    out = np.zeros((n + 63) // 64 * 8 + 8, dtype=np.uint8)
-    out[:(n + 7) // 8] = np.packbits(flags, bitorder="little")
-    return out
-
-
 class Case:
     """Both sides carry x over {0..3} with ~10 % NULLs; the build side also a
     band [lo, hi) with lo in {0..3}, hi = lo + {0..2} and ~10 % NULL lo; two
@@ -158,16 +144,6 @@ def up(ctx, arr):
     return ctx.upload(np.concatenate([raw, np.zeros(16, dtype=np.uint8)]))
 
 
-def term(kind, group, dtype=0, cmp=0, b=None, bv=None, p=None, pv=None):
-    ptr = lambda buf: buf.ptr.value if buf is not None else None  # noqa: E731
-    return gpu.BgJoinFilterTerm(kind, group, dtype, cmp, ptr(b), ptr(bv),
-                                ptr(p), ptr(pv))
-
-
-def terms_array(terms):
-    return (gpu.BgJoinFilterTerm * max(len(terms), 1))(*terms)
-
-
 class Dev:
     """The case's build side on the device, and probe slices on demand."""
 
@@ -208,38 +184,53 @@ class Join:
         assert ctx.L.bg_nljoin_open(n_build, ctypes.byref(self.h)) == BG_OK
         assert self.h.value
 
+    # the handle's five entries after open; HashJoin swaps in the general
+    # hash join's
+    def _count(self, n, jt, terms, nterms, m):
+        return self.ctx.L.bg_nljoin_count(self.h, n, jt, terms, nterms, m)
+
+    def _fill(self, n, jt, terms, nterms, op, ob):
+        return self.ctx.L.bg_nljoin_fill(self.h, n, jt, terms, nterms, op, ob)
+
+    def _mark(self, n, terms, nterms):
+        return self.ctx.L.bg_nljoin_mark(self.h, n, terms, nterms)
+
+    def _build_rows(self, matched, cnt, out):
+        return self.ctx.L.bg_nljoin_build_rows(self.h, matched, cnt, out)
+
+    def _free(self):
+        return self.ctx.L.bg_nljoin_free(self.h)
+
     def mark(self, n, terms, nterms):
-        assert self.ctx.L.bg_nljoin_mark(self.h, n, terms, nterms) == BG_OK
+        assert self._mark(n, terms, nterms) == BG_OK
 
     def rows(self, matched):
         out = self.ctx.alloc(4 * self.n_build + 4)
         cnt = I64(-1)
-        assert self.ctx.L.bg_nljoin_build_rows(
-            self.h, matched, ctypes.byref(cnt), out.ptr) == BG_OK
+        assert self._build_rows(matched, ctypes.byref(cnt), out.ptr) == BG_OK
         return out.download(np.uint32, cnt.value).astype(np.int64).tolist()
 
     def pairs(self, n, jt, terms, nterms):
         """Count, then fill into buffers pre-filled with a sentinel: nothing
         may be written past the reported count.  -> list of (probe, build)
         in the order written."""
-        L, m, pad = self.ctx.L, I64(-1), 8
-        assert L.bg_nljoin_count(self.h, n, jt, terms, nterms,
-                                 ctypes.byref(m)) == BG_OK
+        m, pad = I64(-1), 8
+        assert self._count(n, jt, terms, nterms, ctypes.byref(m)) == BG_OK
         m = m.value
         bufs = []
         for _ in range(2):
             b = self.ctx.alloc(4 * (m + pad))
             b.upload(np.full(m + pad, SENTINEL, dtype=np.uint32))
             bufs.append(b)
-        assert L.bg_nljoin_fill(self.h, n, jt, terms, nterms, bufs[0].ptr,
-                                bufs[1].ptr) == BG_OK
+        assert self._fill(n, jt, terms, nterms, bufs[0].ptr,
+                          bufs[1].ptr) == BG_OK
         got = [b.download(np.uint32, m + pad) for b in bufs]
         for g in got:
             assert np.all(g[m:] == SENTINEL)
         return list(zip(got[0][:m].tolist(), got[1][:m].tolist()))
 
     def free(self):
-        assert self.ctx.L.bg_nljoin_free(self.h) == BG_OK
+        assert self._free() == BG_OK
         self.h = ctypes.c_void_p()
 
 
@@ -460,16 +451,159 @@ def test_refusals_and_pool_balance(ctx):
 
 
 # ---------------------------------------------------------------------------
+# the two handles against each other
+# ---------------------------------------------------------------------------
+class HashJoin(Join):
+    """One bg_hashjoin_build2 handle over a constant Int64 key, through the
+    _filtered entries: every key is equal, so every build row is a candidate
+    of every probe row, as in the nested loop.  bkey / pkey: key_column()."""
+
+    def __init__(self, ctx, n_build, bkey, pkey):
+        self.ctx, self.n_build = ctx, n_build
+        self.bkey, self.pkey = bkey[0], pkey[0]
+        self.h = ctypes.c_void_p()
+        assert ctx.L.bg_hashjoin_build2(self.bkey, 1, n_build,
+                                        ctypes.byref(self.h)) == BG_OK
+        assert self.h.value
+
+    def _count(self, n, jt, terms, nterms, m):
+        return self.ctx.L.bg_hashjoin_probe_count2_filtered(
+            self.h, self.pkey, 1, n, jt, terms, nterms, m)
+
+    def _fill(self, n, jt, terms, nterms, op, ob):
+        return self.ctx.L.bg_hashjoin_probe_fill2_filtered(
+            self.h, self.pkey, 1, n, jt, terms, nterms, op, ob)
+
+    def _mark(self, n, terms, nterms):
+        return self.ctx.L.bg_hashjoin_probe_mark2_filtered(
+            self.h, self.pkey, 1, n, terms, nterms)
+
+    def _build_rows(self, matched, cnt, out):
+        return self.ctx.L.bg_hashjoin_build_rows2(self.h, matched, cnt, out)
+
+    def _free(self):
+        return self.ctx.L.bg_hashjoin_free2(self.h)
+
+
+def key_column(ctx, n):
+    """-> (one all-zero Int64 key column of n rows, its buffer)."""
+    buf = up(ctx, np.zeros(n, dtype=np.int64))
+    return (gpu.BgColumn * 1)(ctx.column(gpu.BG_DT_INT64, buf, n)), buf
+
+
+@contextlib.contextmanager
+def both_handles(ctx, n_build, bkey, pkey):
+    """-> (nested-loop handle, hash handle), both freed on every path."""
+    nl = Join(ctx, n_build)
+    try:
+        hj = HashJoin(ctx, n_build, bkey, pkey)
+        try:
+            yield nl, hj
+        finally:
+            hj.free()
+    finally:
+        nl.free()
+
+
+def by_probe_row(pairs):
+    """Probe-major pairs -> {probe row: its build rows, sorted}."""
+    rows = [p for p, _ in pairs]
+    assert rows == sorted(rows)
+    out = defaultdict(list)
+    for p, b in pairs:
+        out[p].append(b)
+    return {p: sorted(bs) for p, bs in out.items()}
+
+
+# a lone lane, a full wave, a wave plus one, a block (BG_BLOCK in kernels.hip,
+# 256) plus one: where a whole-block loop and its active flag can go wrong
+WALK_N_PROBE = [0, 1, 64, 65, 256 + 1]
+PAIR_TYPES = [INNER, SEMI, ANTI, OUTER_PROBE, OUTER_BUILD, OUTER_FULL]
+
+
+@pytest.mark.parametrize("n_build", [0, 1, 63, 64, 65])
+def test_both_handles_agree(ctx, n_build):
+    """The general hash join on a constant key and the nested-loop join run
+    the same probe kernels over two walks: under one filter (build mask,
+    probe mask, Int64 `lt` with NULLs on both sides) they must report the
+    same totals, the same build rows per probe row and the same visited
+    bits, for every pair type and for mark alone.  Within a probe row the
+    orders differ (chain order against ascending), so rows are compared
+    sorted.  SEMI is the one type where the two may differ by design: each
+    emits the FIRST passing build row of its own order, so there the probe
+    rows must agree, the nested loop's build row must be the lowest passing
+    one and the hash join's some passing one."""
+    b = np.arange(n_build)
+    bx, bxv, bm = (b * 7) % 11, b % 5 != 3, b % 4 != 1
+    dbx, dbxv, dbm = up(ctx, bx), up(ctx, bits(bxv)), up(ctx, bits(bm))
+    bkey = key_column(ctx, n_build)
+    probes = {}
+    for n in WALK_N_PROBE:
+        p = np.arange(n)
+        px, pxv, pm = (p * 5 + 3) % 13, p % 7 != 5, p % 3 != 2
+        if n == 65:
+            # the second wave has exactly one live lane
+            assert pm[64] and pxv[64] and pm[64:].sum() == 1
+        bufs = up(ctx, px), up(ctx, bits(pxv)), up(ctx, bits(pm))
+        terms = [term(gpu.BG_JF_BUILD_MASK, 0, b=dbm),
+                 term(gpu.BG_JF_PROBE_MASK, 0, p=bufs[2]),
+                 term(gpu.BG_JF_CROSS, 0, gpu.BG_DT_INT64, CMP_CODE["lt"],
+                      dbx, dbxv, bufs[0], bufs[1])]
+        passes = ((bm & bxv)[:, None] & (pm & pxv)[None, :] &
+                  (bx[:, None] < px[None, :]))
+        probes[n] = (terms_array(terms), len(terms), key_column(ctx, n),
+                     passes, bufs)
+    gc.collect()
+    base = ctx.pool_stats()[:2]
+
+    for n, (terms, nt, pkey, passes, _keep) in probes.items():
+        ok = {p: np.flatnonzero(passes[:, p]).tolist() for p in range(n)}
+        marked = np.flatnonzero(passes.any(axis=1)).tolist()
+        for jt in PAIR_TYPES:
+            with both_handles(ctx, n_build, bkey, pkey) as (nl, hj):
+                got_nl = nl.pairs(n, jt, terms, nt)
+                got_hj = hj.pairs(n, jt, terms, nt)
+                assert len(got_nl) == len(got_hj), (n, jt)
+                rows_nl, rows_hj = by_probe_row(got_nl), by_probe_row(got_hj)
+                if jt == SEMI:
+                    assert list(rows_nl) == list(rows_hj)
+                    for p in rows_nl:
+                        assert rows_nl[p] == ok[p][:1]
+                        assert len(rows_hj[p]) == 1 and rows_hj[p][0] in ok[p]
+                else:
+                    assert rows_nl == rows_hj, (n, jt)
+                if jt == INNER:     # and both are the filter's pairs
+                    assert got_nl == [(p, b) for p in range(n) for b in ok[p]]
+                fill_marks = jt in (OUTER_BUILD, OUTER_FULL)
+                assert nl.rows(1) == hj.rows(1) == \
+                    (marked if fill_marks else [])
+                nl.mark(n, terms, nt)
+                hj.mark(n, terms, nt)
+                assert nl.rows(1) == hj.rows(1) == marked
+                assert nl.rows(0) == hj.rows(0) == \
+                    sorted(set(range(n_build)) - set(marked))
+        # SEMI_BUILD / ANTI_BUILD: mark alone, then list the build rows
+        with both_handles(ctx, n_build, bkey, pkey) as (nl, hj):
+            nl.mark(n, terms, nt)
+            hj.mark(n, terms, nt)
+            assert nl.rows(1) == hj.rows(1) == marked
+            assert nl.rows(0) == hj.rows(0)
+    if n_build == 65:
+        # on the reference alone: at the largest size the filter leaves rows
+        # matched and unmatched on both sides
+        passes = probes[257][3]
+        assert 0 < passes.any(axis=1).sum() < 65
+        assert 0 < passes.any(axis=0).sum() < 257
+    gc.collect()
+    assert ctx.pool_stats()[:2] == base
+
+
+# ---------------------------------------------------------------------------
 # stage level
 # ---------------------------------------------------------------------------
 def _doc(plan):
     return {"job_id": "job-nlj", "stage_id": 1, "task_id": 0,
             "work_dir": "/tmp/stage-tests", "plan": plan}
-
-
-def scan_of(table, name):
-    return {"op": "scan", "schema": stage.schema_json(table.schema),
-            "source": {"kind": "device", "table": name}}
 
 
 def run(plan):
